@@ -11,6 +11,15 @@ weights, bf16 compute.
 
 Additional benchmarks (not the headline): --model clm-decode measures Perceiver-AR
 KV-cached decode tok/s; --model img / --model flow the big-KV encoders.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K
+steps, print the line. --dump-outputs DIR additionally writes what the last timed
+step computed (loss and logits / flow / generated tokens) as DIR/<name>.npy in
+float32 so two builds can be compared output for output; inputs and init are
+seeded, so equal arguments give equal inputs. Arrays above DUMP_MAX_ELEMS are
+reduced to a fixed seeded sample of their flattened elements. --full is where any
+secondary measurement (anything beyond the headline figure) belongs; there is none
+at present, the other workloads being separate --model runs.
 """
 from __future__ import annotations
 
@@ -38,6 +47,10 @@ def parse_args():
     p.add_argument("--ddp-impl", default="native", choices=["native", "torch"],
                    help="gradient reducer: perceiver_amd.parallel bucketed RCCL reducer or torch DDP")
     p.add_argument("--seed", type=int, default=17)
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write the last step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements beyond the headline figure (none at present)")
     return p.parse_args()
 
 
@@ -61,6 +74,24 @@ def setup_dist(args):
     else:
         device = torch.device("cpu")
     return rank, world_size, device
+
+
+# per-array cap for --dump-outputs: 4Mi fp32 elements = 16 MiB; no bench returns more
+# than three arrays, so a dump stays below 64 MB
+DUMP_MAX_ELEMS = 1 << 22
+
+
+def dump_outputs(outputs, out_dir, seed):
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().to("cpu", torch.float32)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(seed)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.numpy())
 
 
 def barrier_sync(device):
@@ -141,7 +172,11 @@ class MLMBench:
         if getattr(self, "reducer", None) is not None:
             self.reducer.finalize()
         self.opt.step()
+        self.last = {"loss": loss.detach(), "logits": logits.detach()}
         return loss
+
+    def outputs(self):
+        return self.last
 
     def items_per_step(self, world):
         return self.batch * world  # samples
@@ -201,7 +236,10 @@ class CLMTrainBench:
         if getattr(self, "reducer", None) is not None:
             self.reducer.finalize()
         self.opt.step()
+        self.last = {"loss": loss.detach(), "logits": out.logits.detach()}
         return loss
+
+    outputs = MLMBench.outputs
 
     def items_per_step(self, world):
         return self.batch * world
@@ -265,17 +303,24 @@ class CLMDecodeBench:
 
                 self._gd = GraphedDecoder(self.model, self._kv)
         if self.use_graph:
-            self._gd.prefill(self.prompt, prefix_len=self.prompt_len - 1)
-            self._gd.decode(self.decode_steps - 1)
+            first = self._gd.prefill(self.prompt, prefix_len=self.prompt_len - 1)
+            rest = self._gd.decode(self.decode_steps - 1)
+            self.last = [first, rest]
             return None
         for c in self._kv:
             c.reset()
         out = self.model(self.prompt, prefix_len=self.prompt_len - 1, kv_cache=self._kv)
         tok = out.logits[:, -1:].argmax(-1)
+        self.last = [tok]
         for _ in range(self.decode_steps - 1):
             out = self.model(tok, prefix_len=0, kv_cache=self._kv)
             tok = out.logits[:, -1:].argmax(-1)
+            self.last.append(tok)
         return None
+
+    def outputs(self):
+        # the decode_steps generated tokens of the last step, (batch, decode_steps)
+        return {"tokens": torch.cat(self.last, dim=1)}
 
     def items_per_step(self, world):
         return self.batch * self.decode_steps * world  # generated tokens
@@ -341,6 +386,7 @@ class ImgBench(MLMBench):
         if getattr(self, "reducer", None) is not None:
             self.reducer.finalize()
         self.opt.step()
+        self.last = {"loss": loss.detach(), "logits": logits.detach()}
         return loss
 
     def config_json(self):
@@ -392,6 +438,7 @@ class FlowBench(ImgBench):
         if getattr(self, "reducer", None) is not None:
             self.reducer.finalize()
         self.opt.step()
+        self.last = {"loss": loss.detach(), "flow": flow.detach()}
         return loss
 
     def config_json(self):
@@ -428,6 +475,9 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = bench.items_per_step(world) * args.steps / elapsed
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bench.outputs(), args.dump_outputs, args.seed)
 
     if rank == 0:
         cfg = bench.config_json()
