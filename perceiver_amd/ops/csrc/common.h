@@ -59,13 +59,8 @@ DEVINL unsigned short f2bf(float f) {
 // original splitmix64 chain lowered to ~3x the VALU ops, and the hash runs
 // once per attention element — it was a measurable share of the backward
 // kernels' 21:1 VALU:MFMA instruction ratio (profiles/ PMC).
-// Dropout draw mapping: one 32-bit hash yields TWO 16-bit draws for the
-// qi-pair (qi>>1, qi&1) at a given key j; every kernel (fwd, dq, dkv) uses
-// drop16(seed,bh,qi,j) so forward and backward regenerate identical masks.
-// The q-major pairing halves the hash VALU in the three kernels whose inner
-// r-loop walks consecutive qi (fwd pipe, fwd v3, dq — the compiler hoists
-// the shared hash); dkv (ki-major inner loop) pays the same cost as before.
-// Keep threshold is 16-bit: drop_p quantized to 1/65536.
+// How the attention kernels split one hash into per-row 16-bit draws is
+// written once in attn_common.h.
 DEVINL unsigned int rng_hash(unsigned long long seed, int bh, int i, int j) {
     unsigned int x = (unsigned int)seed + (unsigned int)(seed >> 32) * 0x9E3779B9u;
     x += (unsigned int)bh * 0x85EBCA6Bu + (unsigned int)i * 0xC2B2AE35u +
@@ -76,11 +71,6 @@ DEVINL unsigned int rng_hash(unsigned long long seed, int bh, int i, int j) {
     x *= 0x846CA68Bu;
     x ^= x >> 16;
     return x;
-}
-
-DEVINL unsigned int drop16(unsigned long long seed, int bh, int qi, int j) {
-    unsigned int h = rng_hash(seed, bh, qi >> 1, j);
-    return (qi & 1) ? (h >> 16) : (h & 0xffffu);
 }
 
 // erf via the Abramowitz-Stegun 7.1.26 rational approximation (|err| <=
@@ -117,77 +107,3 @@ DEVINL float gelu_grad_f(float x) {
             TORCH_CHECK(false, "HIP kernel launch failed: ", hipGetErrorString(e)); \
         }                                                                           \
     } while (0)
-
-// ---- T14 async-STAGE split helpers (shared by the attention kernels) ----
-// issue: clamped-row unconditional vector loads into registers; the vmcnt
-// waits land at the write call one compute phase later, hiding HBM latency
-// under MFMA work. Valid only when the runtime dims match the template
-// exactly (every granule full-width; callers pad odd dims to the template).
-template <int ROWS_TILE, int DD, int NG>
-DEVINL void issue_tile(short8v (&st)[NG], const unsigned short* __restrict__ src,
-                       long sstride, int row_limit, int tid) {
-    constexpr int GPR = DD / 8;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        int g = tid + i * 256;
-        int row = g / GPR, c0 = (g % GPR) * 8;
-        int rowc = row < row_limit ? row : row_limit - 1;
-        st[i] = *reinterpret_cast<const short8v*>(src + (long)rowc * sstride + c0);
-    }
-}
-
-// write halves: spill staged registers into the row-major and/or 16-column
-// subtiled LDS images, zero-filling clamp-duplicated tail rows
-template <int ROWS_TILE, int DD, int NG>
-DEVINL void write_rm(const short8v (&st)[NG], char* lds_rm, int ldst_bytes,
-                     int rows_valid, int tid) {
-    constexpr int GPR = DD / 8;
-    const bool tail = rows_valid < ROWS_TILE;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        int g = tid + i * 256;
-        // NG rounds up for tiles that don't divide into whole 2048-elem
-        // sweeps (288/352-wide pad tiers); the surplus granules are no-ops
-        if ((ROWS_TILE * DD) % 2048 != 0 && g >= (ROWS_TILE * DD) / 8) continue;
-        int row = g / GPR, c0 = (g % GPR) * 8;
-        short8v val = st[i];
-        if (tail && row >= rows_valid) val = short8v{};
-        *reinterpret_cast<short8v*>(lds_rm + row * ldst_bytes + c0 * 2) = val;
-    }
-}
-
-template <int ROWS_TILE, int DD, int NG>
-DEVINL void write_sub16(const short8v (&st)[NG], char* lds16, int rows_valid, int tid) {
-    constexpr int GPR = DD / 8;
-    constexpr int SUBE = ROWS_TILE * 16 + 8;
-    const bool tail = rows_valid < ROWS_TILE;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        int g = tid + i * 256;
-        if ((ROWS_TILE * DD) % 2048 != 0 && g >= (ROWS_TILE * DD) / 8) continue;
-        int row = g / GPR, c0 = (g % GPR) * 8;
-        short8v val = st[i];
-        if (tail && row >= rows_valid) val = short8v{};
-        *reinterpret_cast<short8v*>(
-            lds16 + ((c0 / 16) * SUBE + row * 16 + (c0 % 16)) * 2) = val;
-    }
-}
-
-template <int ROWS_TILE, int DD, int NG>
-DEVINL void write_rm_sub16_c(const short8v (&st)[NG], char* lds_rm, int ldst_bytes,
-                             char* lds16, int rows_valid, int tid) {
-    constexpr int GPR = DD / 8;
-    constexpr int SUBE = ROWS_TILE * 16 + 8;
-    const bool tail = rows_valid < ROWS_TILE;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        int g = tid + i * 256;
-        if ((ROWS_TILE * DD) % 2048 != 0 && g >= (ROWS_TILE * DD) / 8) continue;
-        int row = g / GPR, c0 = (g % GPR) * 8;
-        short8v val = st[i];
-        if (tail && row >= rows_valid) val = short8v{};
-        *reinterpret_cast<short8v*>(lds_rm + row * ldst_bytes + c0 * 2) = val;
-        *reinterpret_cast<short8v*>(
-            lds16 + ((c0 / 16) * SUBE + row * 16 + (c0 % 16)) * 2) = val;
-    }
-}

@@ -13,10 +13,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <cfloat>
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short short4x;
+#include "attn_common.h"
 
 namespace {
 
@@ -46,107 +43,10 @@ __global__ void delta_kernel(const unsigned short* __restrict__ dout,
     if (lane == 0) delta[row] = acc;
 }
 
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-
-// ---- 16-column-subtiled image + ds_read_b64_tr_b16 (see flash_fwd.hip) ----
-// Replaces the separate transposed staging pass: the image is written ROW-major
-// (one 16-B write per 8-channel granule) and consumed column-major through the
-// hardware transpose read, so the 8-row packed-write pass (and its bank-conflict
-// lockstep) disappears along with the duplicate global re-read.
-template <int ROWS_TILE>
-DEVINL void stage_sub16(const unsigned short* __restrict__ src, long src_stride,
-                        int rows_valid, int d, int d_pad, char* lds, int tid) {
-    constexpr int SUBE = ROWS_TILE * 16 + 8;
-    const int gpr = d_pad / 8;
-    const int total = ROWS_TILE * gpr;
-    for (int g = tid; g < total; g += 256) {
-        int row = g / gpr;
-        int c0 = (g % gpr) * 8;
-        short8v val = {};
-        if (row < rows_valid && c0 < d) {
-            if (c0 + 8 <= d) {
-                val = *reinterpret_cast<const short8v*>(src + (long)row * src_stride + c0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    val[e] = (c0 + e < d) ? (short)src[(long)row * src_stride + c0 + e] : (short)0;
-            }
-        }
-        *reinterpret_cast<short8v*>(
-            lds + ((c0 / 16) * SUBE + row * 16 + (c0 % 16)) * 2) = val;
-    }
-}
-
-// B-fragment rows row0..row0+31, cols 16*sub..: per-lane 8-B loads of one 4x16
-// row-major tile per 16-lane group; the instruction's fixed cross-lane exchange
-// delivers column lo16.
-template <int ROWS_TILE>
-DEVINL bf16x8 read_bfrag_tr16(const char* lds, int sub, int row0, int hi4, int lo16) {
-    constexpr int SUBE = ROWS_TILE * 16 + 8;
-    const __bf16* base = reinterpret_cast<const __bf16*>(lds) +
-                         sub * SUBE + (row0 + hi4 * 8) * 16 + lo16 * 4;
-    auto pp = (__attribute__((address_space(3))) bf16x4*)base;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(pp);
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(pp + 16);  // +4 rows
-    bf16x8 out;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { out[e] = lo[e]; out[e + 4] = hi[e]; }
-    return out;
-}
-
-// stage (rows_tile x d) tile into BOTH the row-major image (row stride
-// ldst_bytes) and the 16-col subtiled image: one global read per granule,
-// two LDS writes (replaces two separate staging passes = half the global
-// load instructions on the q/do/k operands)
-template <int ROWS_TILE>
-DEVINL void stage_rm_sub16(const unsigned short* __restrict__ src, long src_stride,
-                           int rows_valid, int d, int d_pad,
-                           char* lds_rm, int ldst_bytes, char* lds16, int tid) {
-    constexpr int SUBE = ROWS_TILE * 16 + 8;
-    const int gpr = d_pad / 8;
-    const int total = ROWS_TILE * gpr;
-    for (int g = tid; g < total; g += 256) {
-        int row = g / gpr;
-        int c0 = (g % gpr) * 8;
-        short8v val = {};
-        if (row < rows_valid && c0 < d) {
-            if (c0 + 8 <= d) {
-                val = *reinterpret_cast<const short8v*>(src + (long)row * src_stride + c0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    val[e] = (c0 + e < d) ? (short)src[(long)row * src_stride + c0 + e] : (short)0;
-            }
-        }
-        *reinterpret_cast<short8v*>(lds_rm + row * ldst_bytes + c0 * 2) = val;
-        *reinterpret_cast<short8v*>(
-            lds16 + ((c0 / 16) * SUBE + row * 16 + (c0 % 16)) * 2) = val;
-    }
-}
-
-// stage (rows_tile x d) tile row-major into LDS (row stride ldst_bytes), zero-pad
-template <int ROWS_TILE>
-DEVINL void stage_rm(const unsigned short* __restrict__ src, long src_stride,
-                     int rows_valid, int d, int d_pad,
-                     char* lds, int ldst_bytes, int tid) {
-    const int gpr = d_pad / 8;
-    const int total = ROWS_TILE * gpr;
-    for (int g = tid; g < total; g += 256) {
-        int row = g / gpr;
-        int c0 = (g % gpr) * 8;
-        short8v val = {};
-        if (row < rows_valid) {
-            if (c0 + 8 <= d) {
-                val = *reinterpret_cast<const short8v*>(src + (long)row * src_stride + c0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    val[e] = (c0 + e < d) ? (short)src[(long)row * src_stride + c0 + e] : (short)0;
-            }
-        }
-        *reinterpret_cast<short8v*>(lds + row * ldst_bytes + c0 * 2) = val;
-    }
-}
+// Transposed operands (K^T / Q^T / dO^T) are never staged separately: each tile
+// is read from global once and written ROW-major into the row-major image and
+// the 16-column-subtiled image (attn_common.h), the latter consumed
+// column-major through the hardware transpose read.
 
 // ---------------------------------------------------------------- dQ kernel
 // grid.x over Q blocks (QH*16 rows per wave), grid.y = B*H. Stages per TILE-key
@@ -189,15 +89,14 @@ __global__ void flash_dq_kernel(
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int k_stride = d_pad * 2 + 16;
-    const int kt_stride = TILE * 2 + 16;   // (p-buffer row stride)
     const int v_stride = dv_pad * 2 + 16;
+    constexpr int SUBE_T = sub16_elems(TILE);
     char* k_lds = smem;                                  // TILE * k_stride
-    char* kt16_lds = k_lds + TILE * k_stride;            // (DMAX/16) * (TILE*16+8) elems
-    char* v_lds = kt16_lds + (DMAX / 16) * (TILE * 16 + 8) * 2;   // TILE * v_stride
+    char* kt16_lds = k_lds + TILE * k_stride;            // (DMAX/16) * SUBE_T elems
+    char* v_lds = kt16_lds + (DMAX / 16) * SUBE_T * 2;   // TILE * v_stride
     // per-wave transposed dS image ([key][16 q-rows] subtile per h): packed
     // ushort2 writes + ds_read_b64_tr_b16 A-fragment reads (the row-major
     // image needed 32 scalar b16 stores per tile per wave)
-    constexpr int SUBE_T = TILE * 16 + 8;
     char* p_lds = v_lds + TILE * v_stride;               // NWAVES * QH * SUBE_T * 2
     char* p_mine = p_lds + wave * QH * SUBE_T * 2;
 
@@ -209,34 +108,8 @@ __global__ void flash_dq_kernel(
         int qi = q0 + h * 16 + lo16;
         bool valid = qi < Nq;
         int qc = valid ? qi : Nq - 1;
-        const unsigned short* qrow = qbase + (long)qc * qsn;
-        const unsigned short* dorow = dobase + (long)qc * dsn;
-#pragma unroll
-        for (int kb = 0; kb < DMAX / 32; ++kb) {
-            short8v val = {};
-            if (kb < d_blocks && valid) {
-                int c0 = kb * 32 + hi4 * 8;
-                if (c0 + 8 <= D) val = *reinterpret_cast<const short8v*>(qrow + c0);
-                else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) val[e] = (c0 + e < D) ? (short)qrow[c0 + e] : (short)0;
-                }
-            }
-            q_frag[h][kb] = val;
-        }
-#pragma unroll
-        for (int kb = 0; kb < DVMAX / 32; ++kb) {
-            short8v val = {};
-            if (kb < dv_blocks32 && valid) {
-                int c0 = kb * 32 + hi4 * 8;
-                if (c0 + 8 <= Dv) val = *reinterpret_cast<const short8v*>(dorow + c0);
-                else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) val[e] = (c0 + e < Dv) ? (short)dorow[c0 + e] : (short)0;
-                }
-            }
-            do_frag[h][kb] = val;
-        }
+        load_afrag_row(q_frag[h], qbase + (long)qc * qsn, valid, d_blocks, D, hi4);
+        load_afrag_row(do_frag[h], dobase + (long)qc * dsn, valid, dv_blocks32, Dv, hi4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int qi2 = q0 + h * 16 + hi4 * 4 + r;
@@ -262,9 +135,6 @@ __global__ void flash_dq_kernel(
 
     // T14 split staging on exact template matches: K/V loads for tile t+1 fly
     // during tile t's compute instead of serializing between the barriers
-    // dkv stays on the slow stage for the wide pad tiers: fast staging at
-    // 288/352 spilled 37-298 VGPRs (this kernel's accumulators already fill
-    // the file at TILE=32)
     constexpr bool kFast = (DMAX % 32 == 0) && (DVMAX % 32 == 0) && (DMAX <= 64);
     constexpr int NG_K = kFast ? (TILE * DMAX + 2047) / 2048 : 1;
     constexpr int NG_V = kFast ? (TILE * DVMAX + 2047) / 2048 : 1;
@@ -281,15 +151,16 @@ __global__ void flash_dq_kernel(
         int rows_valid = min(TILE, Lk - kv0);
         __syncthreads();
         if (fast) {
-            write_rm_sub16_c<TILE, DMAX>(st_k, k_lds, k_stride, kt16_lds, rows_valid, tid);
-            write_rm<TILE, DVMAX>(st_v, v_lds, v_stride, rows_valid, tid);
+            write_tile<TILE, DMAX, IMG_RM | IMG_SUB16>(st_k, k_lds, k_stride, kt16_lds, rows_valid, tid);
+            write_tile<TILE, DVMAX, IMG_RM>(st_v, v_lds, v_stride, nullptr, rows_valid, tid);
             int kv_n = min(kv0 + TILE, kv_last);
             issue_tile<TILE, DMAX>(st_k, kbase + (long)kv_n * ksn, ksn, Lk - kv_n, tid);
             issue_tile<TILE, DVMAX>(st_v, vbase + (long)kv_n * vsn, vsn, Lk - kv_n, tid);
         } else {
-            stage_rm_sub16<TILE>(kbase + (long)kv0 * ksn, ksn, rows_valid, D, d_pad,
-                                 k_lds, k_stride, kt16_lds, tid);
-            stage_rm<TILE>(vbase + (long)kv0 * vsn, vsn, rows_valid, Dv, dv_pad, v_lds, v_stride, tid);
+            stage_tile<TILE, IMG_RM | IMG_SUB16>(kbase + (long)kv0 * ksn, ksn, rows_valid, D, d_pad,
+                                                 k_lds, k_stride, kt16_lds, tid);
+            stage_tile<TILE, IMG_RM>(vbase + (long)kv0 * vsn, vsn, rows_valid, Dv, dv_pad,
+                                     v_lds, v_stride, nullptr, tid);
         }
         __syncthreads();
         // wave-uniform mask hoist (see flash_fwd.hip): interior tiles of the
@@ -348,17 +219,15 @@ __global__ void flash_dq_kernel(
                 }
                 float4v m4 = {1.f, 1.f, 1.f, 1.f};
                 if (drop_p > 0.f) {
-                    // explicit qi-pair hashes (see common.h drop16 mapping)
-                    int j = kv0 + t * 16 + lo16;
-                    int qb2 = (q0 + h * 16 + hi4 * 4) >> 1;
-                    unsigned int hh[2] = {rng_hash(drop_seed, bh, qb2, j),
-                                          rng_hash(drop_seed, bh, qb2 + 1, j)};
+                    // rows r=0,1 and r=2,3 are the row pairs qb and qb + 2
+                    const int j = kv0 + t * 16 + lo16;
+                    const int qb = q0 + h * 16 + hi4 * 4;
+                    const unsigned int hh[2] = {drop_pair_hash(drop_seed, bh, qb, j),
+                                                drop_pair_hash(drop_seed, bh, qb + 2, j)};
                     const float inv_keep = 1.0f / (1.0f - drop_p);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        unsigned int d = (r & 1) ? (hh[r >> 1] >> 16) : (hh[r >> 1] & 0xffffu);
-                        m4[r] = (d >= drop_thresh) ? inv_keep : 0.f;
-                    }
+                    for (int r = 0; r < 4; ++r)
+                        m4[r] = (drop_half(hh[r >> 1], r) >= drop_thresh) ? inv_keep : 0.f;
                 }
                 float4v ds4 = p4 * (dp_acc[h] * m4 - delta_r[h]);
 #pragma unroll
@@ -375,7 +244,7 @@ __global__ void flash_dq_kernel(
         for (int h = 0; h < QH; ++h)
 #pragma unroll
             for (int t32 = 0; t32 < TBLKS / 2; ++t32)
-                ds_frag[h][t32] = read_bfrag_tr16<TILE>(
+                ds_frag[h][t32] = read_frag_tr16<TILE>(
                     p_mine + h * SUBE_T * 2, 0, t32 * 32, hi4, lo16);
 
         // dQ += dS K : B[k=key][j=ch] via transpose reads of the subtiled K image
@@ -384,7 +253,7 @@ __global__ void flash_dq_kernel(
             if (cb * 16 < d_pad) {
 #pragma unroll
                 for (int t32 = 0; t32 < TBLKS / 2; ++t32) {
-                    bf16x8 bfrag = read_bfrag_tr16<TILE>(kt16_lds, cb, t32 * 32, hi4, lo16);
+                    bf16x8 bfrag = read_frag_tr16<TILE>(kt16_lds, cb, t32 * 32, hi4, lo16);
 #pragma unroll
                     for (int h = 0; h < QH; ++h)
                         dq_acc[h][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -461,18 +330,17 @@ __global__ void flash_dkv_kernel(
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int q_stride = d_pad * 2 + 16;      // Q row-major: TILE rows
-    const int qt_stride = TILE * 2 + 16;      // (p-buffer row stride)
     const int do_stride = dv_pad * 2 + 16;    // dO row-major: TILE rows
+    constexpr int SUBE_T = sub16_elems(TILE);
     char* q_lds = smem;
-    char* q16_lds = q_lds + TILE * q_stride;              // (DMAX/16)*(TILE*16+8) elems
-    char* do_lds = q16_lds + (DMAX / 16) * (TILE * 16 + 8) * 2;
-    char* do16_lds = do_lds + TILE * do_stride;           // (DVMAX/16)*(TILE*16+8) elems
+    char* q16_lds = q_lds + TILE * q_stride;              // (DMAX/16) * SUBE_T elems
+    char* do_lds = q16_lds + (DMAX / 16) * SUBE_T * 2;
+    char* do16_lds = do_lds + TILE * do_stride;           // (DVMAX/16) * SUBE_T elems
     // per-wave transposed P/dS image ([q][16 key-rows] subtile per h) —
     // packed ushort2 writes + tr16 A-fragment reads, see the dq kernel
-    constexpr int SUBE_T = TILE * 16 + 8;
     // two per-wave image halves: P and dS written back-to-back, ONE lgkm
     // wait covers both reads (the second roundtrip stall is gone)
-    char* p_lds = do16_lds + (DVMAX / 16) * (TILE * 16 + 8) * 2;  // NWAVES*2*QH*SUBE_T*2
+    char* p_lds = do16_lds + (DVMAX / 16) * SUBE_T * 2;  // NWAVES*2*QH*SUBE_T*2
     char* p_mine = p_lds + wave * 2 * QH * SUBE_T * 2;
     char* ds_mine = p_mine + QH * SUBE_T * 2;
 
@@ -484,34 +352,8 @@ __global__ void flash_dkv_kernel(
         int ki = k0 + h * 16 + lo16;
         bool valid = ki < Lk;
         int kc = valid ? ki : Lk - 1;
-        const unsigned short* krow = kbase + (long)kc * ksn;
-        const unsigned short* vrow = vbase + (long)kc * vsn;
-#pragma unroll
-        for (int kb = 0; kb < DMAX / 32; ++kb) {
-            short8v val = {};
-            if (kb < d_blocks && valid) {
-                int c0 = kb * 32 + hi4 * 8;
-                if (c0 + 8 <= D) val = *reinterpret_cast<const short8v*>(krow + c0);
-                else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) val[e] = (c0 + e < D) ? (short)krow[c0 + e] : (short)0;
-                }
-            }
-            k_frag[h][kb] = val;
-        }
-#pragma unroll
-        for (int kb = 0; kb < DVMAX / 32; ++kb) {
-            short8v val = {};
-            if (kb < dv_blocks32 && valid) {
-                int c0 = kb * 32 + hi4 * 8;
-                if (c0 + 8 <= Dv) val = *reinterpret_cast<const short8v*>(vrow + c0);
-                else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) val[e] = (c0 + e < Dv) ? (short)vrow[c0 + e] : (short)0;
-                }
-            }
-            v_frag[h][kb] = val;
-        }
+        load_afrag_row(k_frag[h], kbase + (long)kc * ksn, valid, d_blocks, D, hi4);
+        load_afrag_row(v_frag[h], vbase + (long)kc * vsn, valid, dv_blocks32, Dv, hi4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int ki2 = k0 + h * 16 + hi4 * 4 + r;
@@ -554,6 +396,9 @@ __global__ void flash_dkv_kernel(
 
     // T14 split staging (see flash_dq_kernel): Q/dO tile t+1 loads fly under
     // tile t's MFMA work on exact template matches
+    // dkv stays on the slow stage for the wide pad tiers: fast staging at
+    // 288/352 spilled 37-298 VGPRs (this kernel's accumulators already fill
+    // the file at TILE=32).
     // 352 measured SLOWER with fast staging (96 staged VGPRs at occupancy 1
     // starve the S/dP pipeline); 288 gains — img encoder-CA backward
     constexpr bool kFast = (DMAX % 32 == 0) && (DVMAX % 32 == 0) &&
@@ -573,16 +418,16 @@ __global__ void flash_dkv_kernel(
         int rows_valid = min(TILE, Nq - qt0);
         __syncthreads();
         if (fast) {
-            write_rm_sub16_c<TILE, DMAX>(st_q, q_lds, q_stride, q16_lds, rows_valid, tid);
-            write_rm_sub16_c<TILE, DVMAX>(st_do, do_lds, do_stride, do16_lds, rows_valid, tid);
+            write_tile<TILE, DMAX, IMG_RM | IMG_SUB16>(st_q, q_lds, q_stride, q16_lds, rows_valid, tid);
+            write_tile<TILE, DVMAX, IMG_RM | IMG_SUB16>(st_do, do_lds, do_stride, do16_lds, rows_valid, tid);
             int qt_n = min(qt0 + TILE, qt_last);
             issue_tile<TILE, DMAX>(st_q, qbase + (long)qt_n * qsn, qsn, Nq - qt_n, tid);
             issue_tile<TILE, DVMAX>(st_do, dobase + (long)qt_n * dsn, dsn, Nq - qt_n, tid);
         } else {
-            stage_rm_sub16<TILE>(qbase + (long)qt0 * qsn, qsn, rows_valid, D, d_pad,
-                                 q_lds, q_stride, q16_lds, tid);
-            stage_rm_sub16<TILE>(dobase + (long)qt0 * dsn, dsn, rows_valid, Dv, dv_pad,
-                                 do_lds, do_stride, do16_lds, tid);
+            stage_tile<TILE, IMG_RM | IMG_SUB16>(qbase + (long)qt0 * qsn, qsn, rows_valid, D, d_pad,
+                                                 q_lds, q_stride, q16_lds, tid);
+            stage_tile<TILE, IMG_RM | IMG_SUB16>(dobase + (long)qt0 * dsn, dsn, rows_valid, Dv, dv_pad,
+                                                 do_lds, do_stride, do16_lds, tid);
         }
         __syncthreads();
         // wave-uniform mask hoist: interior q-tiles with no padded/overhang
@@ -664,9 +509,9 @@ __global__ void flash_dkv_kernel(
         for (int h = 0; h < QH; ++h)
 #pragma unroll
             for (int t32 = 0; t32 < TBLKS / 2; ++t32) {
-                pt_frag[h][t32] = read_bfrag_tr16<TILE>(
+                pt_frag[h][t32] = read_frag_tr16<TILE>(
                     p_mine + h * SUBE_T * 2, 0, t32 * 32, hi4, lo16);
-                dst_frag[h][t32] = read_bfrag_tr16<TILE>(
+                dst_frag[h][t32] = read_frag_tr16<TILE>(
                     ds_mine + h * SUBE_T * 2, 0, t32 * 32, hi4, lo16);
             }
 
@@ -676,7 +521,7 @@ __global__ void flash_dkv_kernel(
             if (cb * 16 < dv_pad) {
 #pragma unroll
                 for (int t32 = 0; t32 < TBLKS / 2; ++t32) {
-                    bf16x8 bfrag = read_bfrag_tr16<TILE>(do16_lds, cb, t32 * 32, hi4, lo16);
+                    bf16x8 bfrag = read_frag_tr16<TILE>(do16_lds, cb, t32 * 32, hi4, lo16);
 #pragma unroll
                     for (int h = 0; h < QH; ++h)
                         dv_acc[h][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -690,7 +535,7 @@ __global__ void flash_dkv_kernel(
             if (cb * 16 < d_pad) {
 #pragma unroll
                 for (int t32 = 0; t32 < TBLKS / 2; ++t32) {
-                    bf16x8 bfrag = read_bfrag_tr16<TILE>(q16_lds, cb, t32 * 32, hi4, lo16);
+                    bf16x8 bfrag = read_frag_tr16<TILE>(q16_lds, cb, t32 * 32, hi4, lo16);
 #pragma unroll
                     for (int h = 0; h < QH; ++h)
                         dk_acc[h][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -742,7 +587,7 @@ __global__ void flash_dkv_kernel(
 template <int DMAX, int DVMAX, int DQ_TILE, int DQ_QH, int DKV_TILE, int DKV_QH>
 void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const torch::Tensor& k,
                       const torch::Tensor& v, const torch::Tensor& lse, const torch::Tensor& delta,
-                      const c10::optional<torch::Tensor>& pad_mask, bool causal,
+                      const bool* padp, bool causal,
                       float drop_p, unsigned long long drop_seed,
                       torch::Tensor& dq, torch::Tensor& dk, torch::Tensor& dv) {
     int B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
@@ -750,34 +595,22 @@ void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const t
     const int d_pad = (D + 31) & ~31;
     const int dv_pad = (Dv + 31) & ~31;
     auto stream = at::cuda::getCurrentCUDAStream();
-    const bool* padp = nullptr;
-    if (pad_mask.has_value() && pad_mask->defined()) padp = pad_mask->data_ptr<bool>();
+    auto f32 = q.options().dtype(torch::kFloat32);
 
     {   // dQ (with KV-split when the grid would underfill the chip)
-        const int k_stride = d_pad * 2 + 16, kt_stride = DQ_TILE * 2 + 16, v_stride = dv_pad * 2 + 16;
+        const int k_stride = d_pad * 2 + 16, v_stride = dv_pad * 2 + 16;
         const int qblk = 16 * DQ_QH * NWAVES;
-        size_t smem = (size_t)DQ_TILE * k_stride + (size_t)(DMAX / 16) * (DQ_TILE * 16 + 8) * 2 +
-                      (size_t)DQ_TILE * v_stride + (size_t)NWAVES * DQ_QH * (DQ_TILE * 16 + 8) * 2;
+        size_t smem = (size_t)DQ_TILE * k_stride + (size_t)(DMAX / 16) * sub16_elems(DQ_TILE) * 2 +
+                      (size_t)DQ_TILE * v_stride + (size_t)NWAVES * DQ_QH * sub16_elems(DQ_TILE) * 2;
         int gx = (Nq + qblk - 1) / qblk, gy = B * H;
-        int nsplit = 1;
-        long kv_chunk = Lk;
-        if ((long)gx * gy < 512 && Lk > 4 * DQ_TILE) {
-            int want = (int)(512 / ((long)gx * gy)) + 1;
-            int max_split = (Lk + 4 * DQ_TILE - 1) / (4 * DQ_TILE);
-            nsplit = std::min({want, max_split, 32});
-            long tiles = (Lk + DQ_TILE - 1) / DQ_TILE;
-            long tiles_per = (tiles + nsplit - 1) / nsplit;
-            kv_chunk = tiles_per * DQ_TILE;
-            nsplit = (int)((Lk + kv_chunk - 1) / kv_chunk);
-        }
+        const SplitPlan sp = plan_split((long)gx * gy, Lk, DQ_TILE);
         torch::Tensor dq_part;
         float* dq_part_p = nullptr;
-        if (nsplit > 1) {
-            dq_part = torch::empty({(long)nsplit, (long)B * H * Nq, (long)D},
-                                   q.options().dtype(torch::kFloat32));
+        if (sp.nsplit > 1) {
+            dq_part = torch::empty({(long)sp.nsplit, (long)B * H * Nq, (long)D}, f32);
             dq_part_p = dq_part.data_ptr<float>();
         }
-        dim3 grid(gx, gy, nsplit);
+        dim3 grid(gx, gy, sp.nsplit);
         hipLaunchKernelGGL((flash_dq_kernel<DMAX, DVMAX, DQ_TILE, DQ_QH>), grid, dim3(256), smem, stream,
                            reinterpret_cast<const unsigned short*>(q.data_ptr()),
                            reinterpret_cast<const unsigned short*>(k.data_ptr()),
@@ -785,7 +618,7 @@ void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const t
                            reinterpret_cast<const unsigned short*>(dout.data_ptr()),
                            lse.data_ptr<float>(), delta.data_ptr<float>(), padp,
                            reinterpret_cast<unsigned short*>(dq.data_ptr()),
-                           dq_part_p, kv_chunk,
+                           dq_part_p, sp.chunk,
                            q.stride(0), q.stride(1), q.stride(2),
                            k.stride(0), k.stride(1), k.stride(2),
                            v.stride(0), v.stride(1), v.stride(2),
@@ -793,50 +626,30 @@ void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const t
                            dq.stride(0), dq.stride(1), dq.stride(2),
                            B, H, Nq, Lk, D, Dv, (int)causal, drop_p, drop_seed);
         HIP_CHECK_LAST();
-        if (nsplit > 1) {
+        if (sp.nsplit > 1) {
             dq.copy_(dq_part.sum(0).view_as(dq));
         }
     }
     {   // dK/dV (with Q-split when the key grid underfills the chip)
-        const int q_stride = d_pad * 2 + 16, qt_stride = DKV_TILE * 2 + 16;
-        const int do_stride = dv_pad * 2 + 16;
+        const int q_stride = d_pad * 2 + 16, do_stride = dv_pad * 2 + 16;
         const int kblk = 16 * DKV_QH * NWAVES;
-        size_t smem = (size_t)DKV_TILE * q_stride + (size_t)(DMAX / 16) * (DKV_TILE * 16 + 8) * 2 +
-                      (size_t)DKV_TILE * do_stride + (size_t)(DVMAX / 16) * (DKV_TILE * 16 + 8) * 2 +
-                      (size_t)NWAVES * 2 * DKV_QH * (DKV_TILE * 16 + 8) * 2;
+        size_t smem = (size_t)DKV_TILE * q_stride + (size_t)(DMAX / 16) * sub16_elems(DKV_TILE) * 2 +
+                      (size_t)DKV_TILE * do_stride + (size_t)(DVMAX / 16) * sub16_elems(DKV_TILE) * 2 +
+                      (size_t)NWAVES * 2 * DKV_QH * sub16_elems(DKV_TILE) * 2;
         int gx = (Lk + kblk - 1) / kblk, gy = B * H;
-        int nsplit = 1;
-        long q_chunk = Nq;
-        if (!causal && (long)gx * gy < 512 && Nq > 4 * DKV_TILE) {
-            int want = (int)(512 / ((long)gx * gy)) + 1;
-            int max_split = (Nq + 4 * DKV_TILE - 1) / (4 * DKV_TILE);
-            nsplit = std::min({want, max_split, 32});
-            long tiles = (Nq + DKV_TILE - 1) / DKV_TILE;
-            long tiles_per = (tiles + nsplit - 1) / nsplit;
-            q_chunk = tiles_per * DKV_TILE;
-            nsplit = (int)((Nq + q_chunk - 1) / q_chunk);
-        }
+        // causal keeps the whole query axis: each key block starts at its own q_start
+        const SplitPlan sp = causal ? SplitPlan{1, Nq} : plan_split((long)gx * gy, Nq, DKV_TILE);
         torch::Tensor dk_part, dv_part;
         float* dk_part_p = nullptr;
         float* dv_part_p = nullptr;
-        if (nsplit > 1) {
-            dk_part = torch::zeros({(long)nsplit, (long)B * H, (long)Lk, (long)D},
-                                   q.options().dtype(torch::kFloat32));
-            dv_part = torch::zeros({(long)nsplit, (long)B * H, (long)Lk, (long)Dv},
-                                   q.options().dtype(torch::kFloat32));
+        if (sp.nsplit > 1) {
+            dk_part = torch::zeros({(long)sp.nsplit, (long)B * H, (long)Lk, (long)D}, f32);
+            dv_part = torch::zeros({(long)sp.nsplit, (long)B * H, (long)Lk, (long)Dv}, f32);
             dk_part_p = dk_part.data_ptr<float>();
             dv_part_p = dv_part.data_ptr<float>();
         }
-        dim3 grid(gx, gy, nsplit);
-        if (smem > 65536) {
-            static bool raised = [] {
-                (void)hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(&flash_dkv_kernel<DMAX, DVMAX, DKV_TILE, DKV_QH>),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                return true;
-            }();
-            (void)raised;
-        }
+        dim3 grid(gx, gy, sp.nsplit);
+        allow_dynamic_lds<&flash_dkv_kernel<DMAX, DVMAX, DKV_TILE, DKV_QH>>(smem);
         hipLaunchKernelGGL((flash_dkv_kernel<DMAX, DVMAX, DKV_TILE, DKV_QH>), grid, dim3(256), smem, stream,
                            reinterpret_cast<const unsigned short*>(q.data_ptr()),
                            reinterpret_cast<const unsigned short*>(k.data_ptr()),
@@ -845,7 +658,7 @@ void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const t
                            lse.data_ptr<float>(), delta.data_ptr<float>(), padp,
                            reinterpret_cast<unsigned short*>(dk.data_ptr()),
                            reinterpret_cast<unsigned short*>(dv.data_ptr()),
-                           dk_part_p, dv_part_p, q_chunk,
+                           dk_part_p, dv_part_p, sp.chunk,
                            q.stride(0), q.stride(1), q.stride(2),
                            k.stride(0), k.stride(1), k.stride(2),
                            v.stride(0), v.stride(1), v.stride(2),
@@ -854,7 +667,7 @@ void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const t
                            dv.stride(0), dv.stride(1), dv.stride(2),
                            B, H, Nq, Lk, D, Dv, (int)causal, drop_p, drop_seed);
         HIP_CHECK_LAST();
-        if (nsplit > 1) {
+        if (sp.nsplit > 1) {
             dk.copy_(dk_part.sum(0).view_as(dk));
             dv.copy_(dv_part.sum(0).view_as(dv));
         }
@@ -876,12 +689,12 @@ std::vector<torch::Tensor> flash_bwd(torch::Tensor dout, torch::Tensor q, torch:
     if (k.stride(3) != 1) k = k.contiguous();
     if (v.stride(3) != 1) v = v.contiguous();
     int B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
-    int Lk = k.size(2), Dv = v.size(3);
+    int Dv = v.size(3);
 
     // mirror the forward's pad-to-288 shim (see flash_fwd.hip): zero-padded
     // channels are exact — padded dout/out columns contribute 0 to delta, and
     // the padded dq/dk/dv columns are sliced off
-    if (D > 160 && (D != 288 || Dv != 288) && D <= 288 && Dv <= 288) {
+    if (pads_to_288(D, Dv)) {
         namespace F = torch::nn::functional;
         auto res = flash_bwd(F::pad(dout, F::PadFuncOptions({0, 288 - Dv})),
                              F::pad(q, F::PadFuncOptions({0, 288 - D})),
@@ -908,41 +721,38 @@ std::vector<torch::Tensor> flash_bwd(torch::Tensor dout, torch::Tensor q, torch:
         HIP_CHECK_LAST();
     }
 
-    // grads live in merged-heads (B, N, H*D) memory and are returned as the
-    // (B, H, N, D) permuted views: the module's head-merge transpose+reshape
-    // on each grad becomes a free view instead of a 40 MB copy per tensor
-    // (the forward's out uses the same trick)
-    auto dq = torch::empty({q.size(0), q.size(2), q.size(1), q.size(3)}, q.options())
-                  .permute({0, 2, 1, 3});
-    auto dk = torch::empty({k.size(0), k.size(2), k.size(1), k.size(3)}, k.options())
-                  .permute({0, 2, 1, 3});
-    auto dv = torch::empty({v.size(0), v.size(2), v.size(1), v.size(3)}, v.options())
-                  .permute({0, 2, 1, 3});
+    // grads live in merged-heads memory like the forward's out: the module's
+    // head-merge transpose+reshape on each grad becomes a free view instead
+    // of a 40 MB copy per tensor
+    auto dq = empty_merged_heads(q, q.size(3));
+    auto dk = empty_merged_heads(k, k.size(3));
+    auto dv = empty_merged_heads(v, v.size(3));
 
     c10::optional<torch::Tensor> pm;
     if (pad_mask.has_value() && pad_mask->defined()) pm = pad_mask->contiguous();
+    const bool* padp = pad_mask_ptr(pm);
 
     float dp = (float)dropout_p;
     unsigned long long sd = (unsigned long long)seed;
     // <DMAX, DVMAX, DQ_TILE, DQ_QH, DKV_TILE, DKV_QH> — tiles/QH balance LDS
     // occupancy against the 256-VGPR budget per template
     if (D <= 32 && Dv <= 96)
-        launch_flash_bwd<32, 96, 64, 2, 64, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<32, 96, 64, 2, 64, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
     else if (D <= 32 && Dv <= 160)
-        launch_flash_bwd<32, 160, 64, 2, 64, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<32, 160, 64, 2, 64, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
     else if (D <= 64 && Dv <= 64)
-        launch_flash_bwd<64, 64, 64, 2, 64, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<64, 64, 64, 2, 64, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
     else if (D <= 128 && Dv <= 128)
-        launch_flash_bwd<128, 128, 64, 2, 32, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<128, 128, 64, 2, 32, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
     else if (D <= 160 && Dv <= 160)
-        launch_flash_bwd<160, 160, 64, 1, 32, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<160, 160, 64, 1, 32, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
     else if (D <= 288 && Dv <= 288)
         // the img/flow cross-attention class (D = 261, pad 288): dedicated
         // instantiation — the 352 template allocated for 352-wide register
         // arrays and spilled 19 B/lane on dkv
-        launch_flash_bwd<288, 288, 32, 1, 32, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<288, 288, 32, 1, 32, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
     else
-        launch_flash_bwd<352, 352, 32, 1, 32, 1>(dout, q, k, v, lse, delta, pm, causal, dp, sd, dq, dk, dv);
+        launch_flash_bwd<352, 352, 32, 1, 32, 1>(dout, q, k, v, lse, delta, padp, causal, dp, sd, dq, dk, dv);
 
     return {dq, dk, dv};
 }

@@ -24,9 +24,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <cfloat>
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "attn_common.h"
 
 namespace {
 
@@ -34,95 +32,8 @@ constexpr int KVBLK = 64;       // keys per tile
 constexpr int KEYBLKS = KVBLK / 16;
 constexpr int NWAVES = 4;       // waves per workgroup
 
-DEVINL float warp16_max(float x) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) x = fmaxf(x, __shfl_xor(x, m, 64));
-    return x;
-}
-
-DEVINL float warp16_sum(float x) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
-
-// Stage a (KVBLK x D) bf16 tile from global (row stride src_stride elems) into LDS
-// row-major (row stride ldst_bytes), zero-padding col >= d / row >= rows_valid.
-DEVINL void stage_tile_rowmajor(const unsigned short* __restrict__ src, long src_stride,
-                                int rows_valid, int d, int d_pad,
-                                char* lds, int ldst_bytes, int tid) {
-    const int granules_per_row = d_pad / 8;
-    const int total = KVBLK * granules_per_row;
-    for (int g = tid; g < total; g += 256) {
-        int row = g / granules_per_row;
-        int c0 = (g % granules_per_row) * 8;
-        short8v val = {};
-        if (row < rows_valid) {
-            if (c0 + 8 <= d) {
-                val = *reinterpret_cast<const short8v*>(src + (long)row * src_stride + c0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    val[e] = (c0 + e < d) ? (short)src[(long)row * src_stride + c0 + e] : (short)0;
-                }
-            }
-        }
-        *reinterpret_cast<short8v*>(lds + row * ldst_bytes + c0 * 2) = val;
-    }
-}
-
-typedef __attribute__((ext_vector_type(4))) short short4x;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-
-// ---- 16-column-subtiled image + hardware transpose read (guide T10) ----
-// Layout: channel-subtile s holds a (KVBLK x 16) row-major bf16 block with
-// 16-elem (32 B) rows, subtiles padded by 8 elems (16 B) so consecutive
-// subtiles shift LDS banks. ds_read_b64_tr_b16's gather (lane l elem j reads
-// base + (l&15) + j*16 + (l>>4)*64) turns two reads of this image into the
-// 32x16 MFMA B-fragment — V is staged ROW-major (one 16-B write per granule,
-// no 8-row write lockstep: that pattern measured ~11% of wave cycles in bank
-// conflicts) yet consumed column-major for P@V.
-constexpr int SUB_ELEMS = 64 * 16 + 8;  // KVBLK rows x 16 cols + 16-B pad
-
-DEVINL void stage_tile_sub16(const unsigned short* __restrict__ src, long src_stride,
-                             int rows_valid, int dv, int dv_pad,
-                             char* lds, int tid) {
-    const int gpr = dv_pad / 8;
-    const int total = KVBLK * gpr;
-    for (int g = tid; g < total; g += 256) {
-        int row = g / gpr;
-        int c0 = (g % gpr) * 8;
-        short8v val = {};
-        if (row < rows_valid && c0 < dv) {
-            if (c0 + 8 <= dv) {
-                val = *reinterpret_cast<const short8v*>(src + (long)row * src_stride + c0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    val[e] = (c0 + e < dv) ? (short)src[(long)row * src_stride + c0 + e] : (short)0;
-            }
-        }
-        *reinterpret_cast<short8v*>(
-            lds + ((c0 / 16) * SUB_ELEMS + row * 16 + (c0 % 16)) * 2) = val;
-    }
-}
-
-// B-fragment (rows key0..key0+31, cols 16*sub..) from the subtiled image.
-// Per-lane addressing: each 16-lane group loads one 4x16 row-major tile
-// linearly (lane supplies its own 8-B chunk at lo16*4 elems) and the
-// instruction's fixed cross-lane exchange delivers column lo16 to the lane;
-// group hi4 starts at row hi4*8, the second read covers rows +4.
-DEVINL bf16x8 read_bfrag_tr16(const char* lds, int sub, int key0, int hi4, int lo16) {
-    const __bf16* base = reinterpret_cast<const __bf16*>(lds) +
-                         sub * SUB_ELEMS + (key0 + hi4 * 8) * 16 + lo16 * 4;
-    auto p = (__attribute__((address_space(3))) bf16x4*)base;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p + 16);  // +4 rows
-    bf16x8 out;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { out[e] = lo[e]; out[e + 4] = hi[e]; }
-    return out;
-}
+// V image: 16-column subtiles of KVBLK rows (attn_common.h)
+constexpr int SUB_ELEMS = sub16_elems(KVBLK);
 
 // QH: 16-row A-fragments per wave (2 doubles MFMA work per B-fragment LDS read;
 // 1 for the large-D templates where the register budget is spent on O accumulators)
@@ -183,21 +94,7 @@ __global__ void flash_fwd_kernel(            // budget allows (not the 352 templ
         int qi = q0 + h * 16 + lo16;
         bool valid = qi < Nq;
         int qclamp = valid ? qi : Nq - 1;
-        const unsigned short* qrow = qbase + (long)qclamp * qsn;
-#pragma unroll
-        for (int kb = 0; kb < DMAX / 32; ++kb) {
-            short8v val = {};
-            if (kb < d_blocks && valid) {
-                int c0 = kb * 32 + hi4 * 8;
-                if (c0 + 8 <= D) {
-                    val = *reinterpret_cast<const short8v*>(qrow + c0);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) val[e] = (c0 + e < D) ? (short)qrow[c0 + e] : (short)0;
-                }
-            }
-            q_frag[h][kb] = val;
-        }
+        load_afrag_row(q_frag[h], qbase + (long)qclamp * qsn, valid, d_blocks, D, hi4);
     }
 
     // ---- accumulators (C layout: lane holds rows h*16 + hi4*4+r, col lo16 + 16*cb) ----
@@ -249,14 +146,16 @@ __global__ void flash_fwd_kernel(            // budget allows (not the 352 templ
         int rows_valid = min(KVBLK, Lk - kv0);
         __syncthreads();
         if (fast) {
-            write_rm<KVBLK, DMAX>(st_k, k_lds, k_stride, rows_valid, tid);
-            write_sub16<KVBLK, DVMAX>(st_v, v16_lds, rows_valid, tid);
+            write_tile<KVBLK, DMAX, IMG_RM>(st_k, k_lds, k_stride, nullptr, rows_valid, tid);
+            write_tile<KVBLK, DVMAX, IMG_SUB16>(st_v, nullptr, 0, v16_lds, rows_valid, tid);
             int kv_n = min(kv0 + KVBLK, kv_last);
             issue_tile<KVBLK, DMAX>(st_k, kbase + (long)kv_n * ksn, ksn, Lk - kv_n, tid);
             issue_tile<KVBLK, DVMAX>(st_v, vbase + (long)kv_n * vsn, vsn, Lk - kv_n, tid);
         } else {
-            stage_tile_rowmajor(kbase + (long)kv0 * ksn, ksn, rows_valid, D, d_pad, k_lds, k_stride, tid);
-            stage_tile_sub16(vbase + (long)kv0 * vsn, vsn, rows_valid, Dv, dv_pad, v16_lds, tid);
+            stage_tile<KVBLK, IMG_RM>(kbase + (long)kv0 * ksn, ksn, rows_valid, D, d_pad,
+                                      k_lds, k_stride, nullptr, tid);
+            stage_tile<KVBLK, IMG_SUB16>(vbase + (long)kv0 * vsn, vsn, rows_valid, Dv, dv_pad,
+                                         nullptr, 0, v16_lds, tid);
         }
         __syncthreads();
 
@@ -347,15 +246,14 @@ __global__ void flash_fwd_kernel(            // budget allows (not the 352 templ
                     for (int r = 0; r < 4; ++r) pv[r] = __expf(e4[r]);
                     psum4 += float4v{pv[0], pv[1], pv[2], pv[3]};
                     if (drop_p > 0.f) {
-                        int j = kv0 + kb * 16 + lo16;
-                        int qb2 = (q0 + h * 16 + hi4 * 4) >> 1;
-                        unsigned int hh[2] = {rng_hash(drop_seed, bh, qb2, j),
-                                              rng_hash(drop_seed, bh, qb2 + 1, j)};
+                        // rows r=0,1 and r=2,3 are the row pairs qb and qb + 2
+                        const int j = kv0 + kb * 16 + lo16;
+                        const int qb = q0 + h * 16 + hi4 * 4;
+                        const unsigned int hh[2] = {drop_pair_hash(drop_seed, bh, qb, j),
+                                                    drop_pair_hash(drop_seed, bh, qb + 2, j)};
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            unsigned int d = (r & 1) ? (hh[r >> 1] >> 16) : (hh[r >> 1] & 0xffffu);
-                            if (d < drop_thresh) pv[r] = 0.f;
-                        }
+                        for (int r = 0; r < 4; ++r)
+                            if (drop_half(hh[r >> 1], r) < drop_thresh) pv[r] = 0.f;
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -385,7 +283,7 @@ __global__ void flash_fwd_kernel(            // budget allows (not the 352 templ
             if (cb < dv_blocks) {
 #pragma unroll
                 for (int kb32 = 0; kb32 < KEYBLKS / 2; ++kb32) {
-                    bf16x8 bfrag = read_bfrag_tr16(v16_lds, cb, kb32 * 32, hi4, lo16);
+                    bf16x8 bfrag = read_frag_tr16<KVBLK>(v16_lds, cb, kb32 * 32, hi4, lo16);
 #pragma unroll
                     for (int h = 0; h < QH; ++h) {
                         o_acc[h][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -466,23 +364,24 @@ __global__ void flash_merge_kernel(const float* __restrict__ o_part,
     if (lane == 0) lsep[row] = mx + logf(fmaxf(wsum, 1e-37f));
 }
 
-void launch_merge(float* o_part_p, float* lse_part_p, torch::Tensor& out, torch::Tensor& lse,
-                  long rows, int nsplit, int Dv) {
+// fold the KV-split partials into out/lse (nothing to do without a split)
+void merge_fwd_split(const FwdSplit& sp, torch::Tensor& out, torch::Tensor& lse, int Dv) {
+    if (sp.plan.nsplit <= 1) return;
     auto stream = at::cuda::getCurrentCUDAStream();
     int wpb = 4;
-    long blocks = (rows + wpb - 1) / wpb;
+    long blocks = (sp.rows + wpb - 1) / wpb;
     hipLaunchKernelGGL(flash_merge_kernel, dim3(blocks), dim3(64 * wpb), 0, stream,
-                       o_part_p, lse_part_p,
+                       sp.o_part_p, sp.lse_part_p,
                        reinterpret_cast<unsigned short*>(out.data_ptr()),
                        lse.data_ptr<float>(),
                        out.stride(0), out.stride(1), out.stride(2),
-                       (int)out.size(1), (int)out.size(2), rows, nsplit, Dv);
+                       (int)out.size(1), (int)out.size(2), sp.rows, sp.plan.nsplit, Dv);
     HIP_CHECK_LAST();
 }
 
 template <int DMAX, int DVMAX, int QH>
 void launch_flash_fwd(const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
-                      const c10::optional<torch::Tensor>& pad_mask, bool causal,
+                      const bool* padp, bool causal,
                       float drop_p, unsigned long long drop_seed,
                       torch::Tensor& out, torch::Tensor& lse) {
     constexpr int QROWS = 16 * QH;
@@ -494,70 +393,27 @@ void launch_flash_fwd(const torch::Tensor& q, const torch::Tensor& k, const torc
     int vt_stride = KVBLK * 2 + 16;
     size_t smem = (size_t)KVBLK * k_stride + (size_t)(DVMAX / 16) * SUB_ELEMS * 2 +
                   (size_t)NWAVES * QROWS * vt_stride;
-    int gx = (Nq + QBLK - 1) / QBLK;
-    int gy = B * H;
-    // KV-split: aim for ~2 blocks per CU (512 workgroups on 256 CUs)
-    int nsplit = 1;
-    long kv_chunk = Lk;
-    if ((long)gx * gy < 512 && Lk > 4 * KVBLK) {
-        int want = (int)(512 / ((long)gx * gy)) + 1;
-        int max_split = (Lk + 4 * KVBLK - 1) / (4 * KVBLK);  // >= 4 tiles per split
-        nsplit = std::min({want, max_split, 32});
-        long tiles = (Lk + KVBLK - 1) / KVBLK;
-        long tiles_per = (tiles + nsplit - 1) / nsplit;
-        kv_chunk = tiles_per * KVBLK;
-        nsplit = (int)((Lk + kv_chunk - 1) / kv_chunk);
-    }
-    dim3 grid(gx, gy, nsplit);
-    const bool* padp = nullptr;
-    if (pad_mask.has_value() && pad_mask->defined()) {
-        padp = pad_mask->data_ptr<bool>();
-    }
+    // the QH = 1 templates have 64-row workgroups, so their grid (and with it
+    // the split plan) differs from the 128-row QH = 2 and pipelined kernels
+    const FwdSplit sp = make_fwd_split(q, Lk, Dv, QBLK, KVBLK);
+    dim3 grid((Nq + QBLK - 1) / QBLK, B * H, sp.plan.nsplit);
     auto stream = at::cuda::getCurrentCUDAStream();
-    torch::Tensor o_part, lse_part;
-    float* o_part_p = nullptr;
-    float* lse_part_p = nullptr;
-    long rows = (long)B * H * Nq;
-    if (nsplit > 1) {
-        o_part = torch::empty({(long)nsplit, rows, (long)Dv}, q.options().dtype(torch::kFloat32));
-        lse_part = torch::empty({(long)nsplit, rows}, q.options().dtype(torch::kFloat32));
-        o_part_p = o_part.data_ptr<float>();
-        lse_part_p = lse_part.data_ptr<float>();
-    }
     hipLaunchKernelGGL((flash_fwd_kernel<DMAX, DVMAX, QH>), grid, dim3(256), smem, stream,
                        reinterpret_cast<const unsigned short*>(q.data_ptr()),
                        reinterpret_cast<const unsigned short*>(k.data_ptr()),
                        reinterpret_cast<const unsigned short*>(v.data_ptr()),
                        padp,
                        reinterpret_cast<unsigned short*>(out.data_ptr()),
-                       lse.data_ptr<float>(), o_part_p, lse_part_p, kv_chunk,
+                       lse.data_ptr<float>(), sp.o_part_p, sp.lse_part_p, sp.plan.chunk,
                        q.stride(0), q.stride(1), q.stride(2),
                        k.stride(0), k.stride(1), k.stride(2),
                        v.stride(0), v.stride(1), v.stride(2),
                        out.stride(0), out.stride(1), out.stride(2),
                        B, H, Nq, Lk, D, Dv, (int)causal, drop_p, drop_seed);
     HIP_CHECK_LAST();
-    if (nsplit > 1) {
-        launch_merge(o_part_p, lse_part_p, out, lse, rows, nsplit, Dv);
-    }
+    merge_fwd_split(sp, out, lse, Dv);
 }
 
-}  // namespace
-
-bool flash_supported_impl(long d_qk, long d_v, long needs_dropout) {
-    (void)needs_dropout;  // in-kernel counter-hash dropout
-    return d_qk <= 352 && d_v <= 352;
-}
-
-// Deep-pipelined forward (flash_fwd_pipe.hip) for the regular head-dim regimes
-bool flash_fwd_pipe_applicable(long D, long Dv, long Nq);
-void flash_fwd_pipe_launch(const torch::Tensor& q, const torch::Tensor& k,
-                           const torch::Tensor& v, const bool* padp, bool causal,
-                           float drop_p, unsigned long long drop_seed,
-                           torch::Tensor& out, torch::Tensor& lse,
-                           float* o_part_p, float* lse_part_p, long kv_chunk, int nsplit);
-
-namespace {
 bool pipe_enabled() {
     static int v = [] {
         const char* e = getenv("PERCEIVER_NO_PIPE");
@@ -565,7 +421,20 @@ bool pipe_enabled() {
     }();
     return v != 0;
 }
+
 }  // namespace
+
+bool flash_supported_impl(long d_qk, long d_v) {
+    // dropout never narrows the gate: it runs in-kernel (counter-hash draws)
+    return d_qk <= 352 && d_v <= 352;
+}
+
+// host-only view of the split planner, so its contract is testable without a GPU
+std::tuple<int64_t, int64_t> flash_split_plan(int64_t blocks, int64_t len, int64_t tile) {
+    TORCH_CHECK(blocks > 0 && len >= 0 && tile > 0, "flash_split_plan: bad arguments");
+    SplitPlan p = plan_split(blocks, len, (int)tile);
+    return {p.nsplit, p.chunk};
+}
 
 std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                      c10::optional<torch::Tensor> pad_mask, bool causal,
@@ -579,13 +448,12 @@ std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k, torch::Te
     if (k.stride(3) != 1) k = k.contiguous();
     if (v.stride(3) != 1) v = v.contiguous();
     int D = q.size(3), Dv = v.size(3);
-    TORCH_CHECK(flash_supported_impl(D, Dv, 0), "flash_fwd: unsupported head dims ", D, " ", Dv);
+    TORCH_CHECK(flash_supported_impl(D, Dv), "flash_fwd: unsupported head dims ", D, " ", Dv);
 
-    // odd large head dims (the img/flow D=261 class) run as the 288 template
-    // with zero-padded channels: exact for attention (zero K/Q columns add 0
-    // to scores; zero V columns are sliced off), and the exact template match
-    // unlocks the T14 fast staging path
-    if (D > 160 && (D != 288 || Dv != 288) && D <= 288 && Dv <= 288) {
+    // pad-to-288 shim: exact for attention (zero K/Q columns add 0 to scores;
+    // zero V columns are sliced off), and the exact template match unlocks
+    // the T14 fast staging path
+    if (pads_to_288(D, Dv)) {
         namespace F = torch::nn::functional;
         auto q288 = F::pad(q, F::PadFuncOptions({0, 288 - D}));
         auto k288 = F::pad(k, F::PadFuncOptions({0, 288 - D}));
@@ -594,11 +462,8 @@ std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k, torch::Te
         return {res[0].narrow(-1, 0, Dv), res[1]};
     }
 
-    // out lives in merged-heads (B, N, H, Dv) memory and is returned as the
-    // (B, H, N, Dv) permuted view: the module's transpose+reshape after
-    // attention then costs nothing (it was a 42 MB copy per layer on MLM)
-    auto out = torch::empty({q.size(0), q.size(2), q.size(1), (long)Dv}, q.options())
-                   .permute({0, 2, 1, 3});
+    // out lives in merged-heads memory (it was a 42 MB copy per layer on MLM)
+    auto out = empty_merged_heads(q, Dv);
     auto lse = torch::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(torch::kFloat32));
     if (q.numel() == 0 || k.numel() == 0) {
         // degenerate shapes fall back to the eager path upstream; just return zeros
@@ -611,50 +476,25 @@ std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k, torch::Te
     if (pad_mask.has_value() && pad_mask->defined()) {
         pm = pad_mask->contiguous();
     }
+    const bool* padp = pad_mask_ptr(pm);
 
     float dp = (float)dropout_p;
     unsigned long long sd = (unsigned long long)seed;
 
+    // deep-pipelined forward (flash_fwd_pipe.hip) for the regular head-dim regimes
     if (pipe_enabled() && flash_fwd_pipe_applicable(D, Dv, q.size(2))) {
-        int B = q.size(0), H = q.size(1), Nq = q.size(2), Lk = k.size(2);
-        constexpr int PIPE_QBLK = 128;
-        constexpr int KVB = 64;
-        long gx = (Nq + PIPE_QBLK - 1) / PIPE_QBLK;
-        long gy = (long)B * H;
-        int nsplit = 1;
-        long kv_chunk = Lk;
-        if (gx * gy < 512 && Lk > 4 * KVB) {
-            int want = (int)(512 / (gx * gy)) + 1;
-            int max_split = (Lk + 4 * KVB - 1) / (4 * KVB);
-            nsplit = std::min({want, max_split, 32});
-            long tiles = (Lk + KVB - 1) / KVB;
-            long tiles_per = (tiles + nsplit - 1) / nsplit;
-            kv_chunk = tiles_per * KVB;
-            nsplit = (int)((Lk + kv_chunk - 1) / kv_chunk);
-        }
-        torch::Tensor o_part, lse_part;
-        float* o_part_p = nullptr;
-        float* lse_part_p = nullptr;
-        long rows = (long)B * H * Nq;
-        if (nsplit > 1) {
-            o_part = torch::empty({(long)nsplit, rows, (long)Dv}, q.options().dtype(torch::kFloat32));
-            lse_part = torch::empty({(long)nsplit, rows}, q.options().dtype(torch::kFloat32));
-            o_part_p = o_part.data_ptr<float>();
-            lse_part_p = lse_part.data_ptr<float>();
-        }
-        const bool* padp = (pm.has_value() && pm->defined()) ? pm->data_ptr<bool>() : nullptr;
-        flash_fwd_pipe_launch(q, k, v, padp, causal, dp, sd, out, lse,
-                              o_part_p, lse_part_p, kv_chunk, nsplit);
-        if (nsplit > 1) launch_merge(o_part_p, lse_part_p, out, lse, rows, nsplit, Dv);
+        const FwdSplit sp = make_fwd_split(q, k.size(2), Dv, FLASH_PIPE_QBLK, KVBLK);
+        flash_fwd_pipe_launch(q, k, v, padp, causal, dp, sd, out, lse, sp);
+        merge_fwd_split(sp, out, lse, Dv);
         return {out, lse};
     }
 
-    if (D <= 32 && Dv <= 160)       launch_flash_fwd<32, 160, 2>(q, k, v, pm, causal, dp, sd, out, lse);
-    else if (D <= 64 && Dv <= 64)   launch_flash_fwd<64, 64, 2>(q, k, v, pm, causal, dp, sd, out, lse);
-    else if (D <= 128 && Dv <= 128) launch_flash_fwd<128, 128, 2>(q, k, v, pm, causal, dp, sd, out, lse);
-    else if (D <= 160 && Dv <= 160) launch_flash_fwd<160, 160, 1>(q, k, v, pm, causal, dp, sd, out, lse);
-    else if (D <= 288 && Dv <= 288) launch_flash_fwd<288, 288, 1>(q, k, v, pm, causal, dp, sd, out, lse);
-    else                            launch_flash_fwd<352, 352, 1>(q, k, v, pm, causal, dp, sd, out, lse);
+    if (D <= 32 && Dv <= 160)       launch_flash_fwd<32, 160, 2>(q, k, v, padp, causal, dp, sd, out, lse);
+    else if (D <= 64 && Dv <= 64)   launch_flash_fwd<64, 64, 2>(q, k, v, padp, causal, dp, sd, out, lse);
+    else if (D <= 128 && Dv <= 128) launch_flash_fwd<128, 128, 2>(q, k, v, padp, causal, dp, sd, out, lse);
+    else if (D <= 160 && Dv <= 160) launch_flash_fwd<160, 160, 1>(q, k, v, padp, causal, dp, sd, out, lse);
+    else if (D <= 288 && Dv <= 288) launch_flash_fwd<288, 288, 1>(q, k, v, padp, causal, dp, sd, out, lse);
+    else                            launch_flash_fwd<352, 352, 1>(q, k, v, padp, causal, dp, sd, out, lse);
 
     return {out, lse};
 }

@@ -24,15 +24,11 @@
 // filled with -FLT_MAX, right-aligned causal (j > Lk - Nq + i masked), online
 // softmax with rescale-skip, in-kernel counter-hash dropout, KV-split partials
 // merged by the caller's flash_merge kernel. Reference semantics:
-// /root/reference/perceiver/model/core/modules.py:130-166.
+// eager_attention in perceiver_amd/ops/attention.py.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <cfloat>
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) short short4x;
+#include "attn_common.h"
 
 namespace {
 
@@ -42,33 +38,10 @@ constexpr int NWAVES = 4;
 constexpr int QH = 2;            // 16-row q fragments per wave
 constexpr int QROWS = 16 * QH;   // 32 q rows per wave
 constexpr int QBLK = QROWS * NWAVES;
-constexpr int SUB_ELEMS = KVBLK * 16 + 8;  // 16-col subtile + 16-B bank shift
-
-DEVINL float warp16_max(float x) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) x = fmaxf(x, __shfl_xor(x, m, 64));
-    return x;
-}
-
-DEVINL float warp16_sum(float x) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
-
-// B/A fragment via hardware transpose read of a [KVBLK][16] row-major image
-// (V channel subtiles and the transposed-P image share this layout).
-DEVINL bf16x8 read_frag_tr16(const char* lds, int sub, int key0, int hi4, int lo16) {
-    const __bf16* base = reinterpret_cast<const __bf16*>(lds) +
-                         sub * SUB_ELEMS + (key0 + hi4 * 8) * 16 + lo16 * 4;
-    auto p = (__attribute__((address_space(3))) bf16x4*)base;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p + 16);  // +4 keys
-    bf16x8 out;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { out[e] = lo[e]; out[e + 4] = hi[e]; }
-    return out;
-}
+static_assert(QBLK == FLASH_PIPE_QBLK, "flash_fwd() plans the KV split with FLASH_PIPE_QBLK");
+// V channel subtiles and the transposed-P image share the 16-column-subtiled
+// layout (attn_common.h)
+constexpr int SUB_ELEMS = sub16_elems(KVBLK);
 
 // One K/V/bias staging step, register half (issue): clamped-row loads so the
 // loads are unconditional (a per-element load guard would make hipcc branch
@@ -118,6 +91,9 @@ DEVINL void stage_issue(Staged<KGR, VGR, DMAX, DVMAX>& st,
 // needs no zeroing (S is masked via bias), V garbage is killed by P == 0
 // except for fully-masked rows, where the reference's degrade-to-uniform
 // contract needs V rows zeroed — tail tiles pay a small select chain.
+// Kept private to this kernel (same images as write_tile in attn_common.h):
+// routed through the shared template, the register allocation of six of the
+// eight instantiations moved.
 template <int KGR, int VGR, int DMAX, int DVMAX>
 DEVINL void stage_write(const Staged<KGR, VGR, DMAX, DVMAX>& st,
                         char* k_lds, char* v_lds, float* bias_lds,
@@ -258,10 +234,10 @@ __global__ void flash_fwd_pipe_kernel(
             bf16x8 a_frag[QH];
 #pragma unroll
             for (int h = 0; h < QH; ++h)
-                a_frag[h] = read_frag_tr16(p_mine, h, kb32 * 32, hi4, lo16);
+                a_frag[h] = read_frag_tr16<KVBLK>(p_mine, h, kb32 * 32, hi4, lo16);
 #pragma unroll
             for (int cb = 0; cb < CBLOCKS; ++cb) {
-                bf16x8 bfrag = read_frag_tr16(v_buf, cb, kb32 * 32, hi4, lo16);
+                bf16x8 bfrag = read_frag_tr16<KVBLK>(v_buf, cb, kb32 * 32, hi4, lo16);
 #pragma unroll
                 for (int h = 0; h < QH; ++h) {
                     o_acc[h][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -367,17 +343,14 @@ __global__ void flash_fwd_pipe_kernel(
                 for (int r = 0; r < 4; ++r) pv[r] = __expf(e4[r]);
                 psum4 += float4v{pv[0], pv[1], pv[2], pv[3]};
                 if (drop_p > 0.f) {
-                    // explicit qi-pair hashes (qi base is a multiple of 4, so
-                    // rows r=0,1 and r=2,3 share one 32-bit hash each)
-                    int j = kv0 + kb * 16 + lo16;
-                    int qb2 = (q0 + h * 16 + hi4 * 4) >> 1;
-                    unsigned int hh[2] = {rng_hash(drop_seed, bh, qb2, j),
-                                          rng_hash(drop_seed, bh, qb2 + 1, j)};
+                    // rows r=0,1 and r=2,3 are the row pairs qb and qb + 2
+                    const int j = kv0 + kb * 16 + lo16;
+                    const int qb = q0 + h * 16 + hi4 * 4;
+                    const unsigned int hh[2] = {drop_pair_hash(drop_seed, bh, qb, j),
+                                                drop_pair_hash(drop_seed, bh, qb + 2, j)};
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        unsigned int d = (r & 1) ? (hh[r >> 1] >> 16) : (hh[r >> 1] & 0xffffu);
-                        if (d < drop_thresh) pv[r] = 0.f;
-                    }
+                    for (int r = 0; r < 4; ++r)
+                        if (drop_half(hh[r >> 1], r) < drop_thresh) pv[r] = 0.f;
                 }
                 unsigned short* dst = reinterpret_cast<unsigned short*>(
                     p_mine + (h * SUB_ELEMS + (kb * 16 + lo16) * 16 + hi4 * 4) * 2);
@@ -481,12 +454,17 @@ __global__ void flash_fwd_pipe_kernel(
 // The packed-P / bias / dwordx4-epilogue layouts assume EXACT template dims
 // (the kernel reads/writes DVMAX columns unconditionally), so only the
 // instantiated (D, Dv) pairs qualify; anything else falls back to the v3
-// kernel. Nq >= QBLK keeps every wave's q fragment populated.
+// kernel. This list is the only place a pair is named: the gate and the
+// dispatch below are both generated from it.
+#define FLASH_PIPE_TEMPLATES(X) \
+    X(32, 32) X(32, 64) X(32, 96) X(32, 128) X(32, 160) X(64, 64) X(64, 128) X(128, 128)
+
+// Nq >= QBLK keeps every wave's q fragment populated.
 bool flash_fwd_pipe_applicable(long D, long Dv, long Nq) {
     if (Nq < QBLK) return false;
-    if (D == 32) return Dv == 32 || Dv == 64 || Dv == 96 || Dv == 128 || Dv == 160;
-    if (D == 64) return Dv == 64 || Dv == 128;
-    if (D == 128) return Dv == 128;
+#define X(d, dv) if (D == d && Dv == dv) return true;
+    FLASH_PIPE_TEMPLATES(X)
+#undef X
     return false;
 }
 
@@ -494,8 +472,7 @@ namespace {
 template <int DMAX, int DVMAX>
 void launch_pipe(const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
                  const bool* padp, bool causal, float drop_p, unsigned long long drop_seed,
-                 torch::Tensor& out, torch::Tensor& lse,
-                 float* o_part_p, float* lse_part_p, long kv_chunk, int nsplit) {
+                 torch::Tensor& out, torch::Tensor& lse, const FwdSplit& split) {
     int B = q.size(0), H = q.size(1), Nq = q.size(2);
     int Lk = k.size(2);
     constexpr int K_STRIDE = DMAX * 2 + 16;
@@ -504,19 +481,9 @@ void launch_pipe(const torch::Tensor& q, const torch::Tensor& k, const torch::Te
                   NWAVES * QH * SUB_ELEMS * 2 + 2 * KVBLK * sizeof(float);
     size_t smem_epi = (size_t)NWAVES * QROWS * DVMAX * 2;
     if (smem_epi > smem) smem = smem_epi;
-    if (smem > 65536) {
-        // dynamic-LDS requests above the 64 KiB default need the opt-in
-        // (the CU has 160 KiB; we run 1 block/CU)
-        static bool raised = [] {
-            hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&flash_fwd_pipe_kernel<DMAX, DVMAX>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            return true;
-        }();
-        (void)raised;
-    }
+    allow_dynamic_lds<&flash_fwd_pipe_kernel<DMAX, DVMAX>>(smem);
     int gx = (Nq + QBLK - 1) / QBLK;
-    dim3 grid(gx, B * H, nsplit);
+    dim3 grid(gx, B * H, split.plan.nsplit);
     auto stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL((flash_fwd_pipe_kernel<DMAX, DVMAX>), grid, dim3(256), smem, stream,
                        reinterpret_cast<const unsigned short*>(q.data_ptr()),
@@ -524,7 +491,7 @@ void launch_pipe(const torch::Tensor& q, const torch::Tensor& k, const torch::Te
                        reinterpret_cast<const unsigned short*>(v.data_ptr()),
                        padp,
                        reinterpret_cast<unsigned short*>(out.data_ptr()),
-                       lse.data_ptr<float>(), o_part_p, lse_part_p, kv_chunk,
+                       lse.data_ptr<float>(), split.o_part_p, split.lse_part_p, split.plan.chunk,
                        q.stride(0), q.stride(1), q.stride(2),
                        k.stride(0), k.stride(1), k.stride(2),
                        v.stride(0), v.stride(1), v.stride(2),
@@ -534,22 +501,15 @@ void launch_pipe(const torch::Tensor& q, const torch::Tensor& k, const torch::Te
 }
 }  // namespace
 
-// Launch the pipelined forward. Caller guarantees flash_fwd_pipe_applicable()
-// and provides the split-partial buffers when nsplit > 1 (merged by the
-// caller's flash_merge kernel, same contract as the v3 kernel).
 void flash_fwd_pipe_launch(const torch::Tensor& q, const torch::Tensor& k,
                            const torch::Tensor& v, const bool* padp, bool causal,
                            float drop_p, unsigned long long drop_seed,
-                           torch::Tensor& out, torch::Tensor& lse,
-                           float* o_part_p, float* lse_part_p, long kv_chunk, int nsplit) {
+                           torch::Tensor& out, torch::Tensor& lse, const FwdSplit& split) {
     int D = q.size(3), Dv = v.size(3);
-    if (D == 32 && Dv == 32)        launch_pipe<32, 32>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 32 && Dv == 64)   launch_pipe<32, 64>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 32 && Dv == 96)   launch_pipe<32, 96>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 32 && Dv == 128)  launch_pipe<32, 128>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 32 && Dv == 160)  launch_pipe<32, 160>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 64 && Dv == 64)   launch_pipe<64, 64>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 64 && Dv == 128)  launch_pipe<64, 128>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else if (D == 128 && Dv == 128) launch_pipe<128, 128>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, o_part_p, lse_part_p, kv_chunk, nsplit);
-    else TORCH_CHECK(false, "flash_fwd_pipe: no template for D=", D, " Dv=", Dv);
+#define X(d, dv)              \
+    if (D == d && Dv == dv)   \
+        return launch_pipe<d, dv>(q, k, v, padp, causal, drop_p, drop_seed, out, lse, split);
+    FLASH_PIPE_TEMPLATES(X)
+#undef X
+    TORCH_CHECK(false, "flash_fwd_pipe: no template for D=", D, " Dv=", Dv);
 }

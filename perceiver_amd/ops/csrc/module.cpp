@@ -15,7 +15,9 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor w, c10::optiona
                                   double eps);
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w,
                                   torch::Tensor mean, torch::Tensor rstd, bool needs_dwdb);
-bool flash_supported_impl(long d_qk, long d_v, long needs_dropout);
+bool flash_supported_impl(long d_qk, long d_v);
+std::tuple<int64_t, int64_t> flash_split_plan(int64_t blocks, int64_t len, int64_t tile);
+bool flash_fwd_pipe_applicable(long D, long Dv, long Nq);
 void adamw_step(torch::Tensor master, torch::Tensor m, torch::Tensor v, torch::Tensor g,
                 double lr, double beta1, double beta2, double eps, double weight_decay,
                 int64_t step);
@@ -34,7 +36,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_bwd", &gelu_bias_bwd, "fused bias+GELU backward (bf16)");
     m.def("flash_fwd", &flash_fwd, "fused flash attention forward");
     m.def("flash_bwd", &flash_bwd, "fused flash attention backward");
-    m.def("flash_supported", &flash_supported_impl, "shape gate for the flash kernel");
+    // needs_dropout is kept for callers; dropout runs in-kernel and never narrows the gate
+    m.def("flash_supported", [](int64_t d_qk, int64_t d_v, int64_t /*needs_dropout*/) {
+        return flash_supported_impl(d_qk, d_v);
+    }, "shape gate for the flash kernel");
+    m.def("flash_split_plan", &flash_split_plan,
+          "host-only: (nsplit, chunk) of the gridDim.z split for blocks workgroups over a len-long axis");
+    m.def("flash_fwd_pipe_applicable", [](int64_t d, int64_t dv, int64_t nq) {
+        return flash_fwd_pipe_applicable(d, dv, nq);
+    }, "host-only: whether the pipelined forward has a template for (D, Dv) at Nq queries");
     m.def("ln_fwd", &ln_fwd, "fused bf16 LayerNorm forward");
     m.def("ln_bwd", &ln_bwd, "fused bf16 LayerNorm backward");
     m.def("adamw_step", &adamw_step, "single-pass fused AdamW on flat fp32 state");

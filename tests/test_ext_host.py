@@ -17,7 +17,8 @@ def _ext():
 
 def test_extension_loads_and_exposes_api():
     ext = _ext()
-    for name in ["flash_fwd", "flash_bwd", "flash_supported", "ln_fwd", "ln_bwd",
+    for name in ["flash_fwd", "flash_bwd", "flash_supported", "flash_split_plan",
+                 "flash_fwd_pipe_applicable", "ln_fwd", "ln_bwd",
                  "adamw_step", "rotary_apply", "dropout_add_fwd", "dropout_add_bwd",
                  "colsum_bf16", "gemm_bt", "gemm_bt_gelu", "gemm_bt_applicable",
                  "transpose_bf16", "gelu_bias_fwd", "gelu_bias_bwd"]:
@@ -44,3 +45,48 @@ def test_flash_supported_host_gate():
     ext = _ext()
     assert ext.flash_supported(32, 160, 0)
     assert ext.flash_supported(64, 64, 0)
+
+
+@pytest.mark.parametrize("blocks,length,tile,expected", [
+    (1, 4096, 64, (16, 256)),
+    (1, 500, 64, (2, 256)),
+    (8, 50176, 64, (32, 1600)),
+    (1, 200, 32, (2, 128)),
+    (1, 2048, 64, (8, 256)),
+    (512, 4096, 64, (1, 4096)),
+])
+def test_flash_split_plan_pinned(blocks, length, tile, expected):
+    assert tuple(_ext().flash_split_plan(blocks, length, tile)) == expected
+
+
+def test_flash_split_plan_invariants():
+    ext = _ext()
+    for blocks in (1, 3, 64, 511, 512):
+        for length in (1, 63, 256, 257, 500, 4096, 182528):
+            for tile in (32, 64):
+                nsplit, chunk = ext.flash_split_plan(blocks, length, tile)
+                case = (blocks, length, tile, nsplit, chunk)
+                assert 1 <= nsplit <= 32, case
+                if nsplit > 1:
+                    assert chunk % tile == 0, case
+                assert nsplit * chunk >= length, case
+                assert (nsplit - 1) * chunk < length, case  # no empty split
+                if blocks >= 512 or length <= 4 * tile:
+                    assert nsplit == 1, case
+
+
+PIPE_TEMPLATES = [(32, 32), (32, 64), (32, 96), (32, 128), (32, 160),
+                  (64, 64), (64, 128), (128, 128)]
+
+
+def test_flash_fwd_pipe_applicable_template_list():
+    ext = _ext()
+    for d, dv in PIPE_TEMPLATES:
+        assert ext.flash_fwd_pipe_applicable(d, dv, 128), (d, dv)
+        assert not ext.flash_fwd_pipe_applicable(d, dv, 127), (d, dv)
+    # exactly those eight: no other pair on the 16-channel grid up to 352 qualifies
+    for d in range(16, 353, 16):
+        for dv in range(16, 353, 16):
+            assert ext.flash_fwd_pipe_applicable(d, dv, 128) == ((d, dv) in PIPE_TEMPLATES), (d, dv)
+    for d, dv in [(48, 80), (32, 48), (128, 64), (261, 261)]:
+        assert not ext.flash_fwd_pipe_applicable(d, dv, 128), (d, dv)

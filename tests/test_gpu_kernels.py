@@ -697,3 +697,102 @@ def test_flash_padded_288_class_matches_autograd():
             err = (got.float() - want).abs().max().item()
             scale = want.abs().max().item() + 1e-6
             assert err / scale < 5e-2, (d, err / scale)
+
+
+def _assert_grads_close(got, want):
+    for g, w, name in zip(got, want, ("dq", "dk", "dv")):
+        err = (g.float() - w).abs().max().item()
+        scale = w.abs().max().item() + 1e-6
+        assert err / scale < 5e-2, f"{name} rel err {err/scale:.4f} (abs {err:.4f})"
+
+
+@pytest.mark.parametrize("shape", [
+    (1, 2, 40, 70, 20, 44),      # small templates, row tail + column tail
+    (1, 1, 48, 100, 322, 322),   # flow class on the 352 template
+])
+def test_flash_partial_granule_fwd_bwd(shape):
+    # neither head dim is a multiple of 8: the element-wise tail of the guarded
+    # tile staging and of the guarded A-fragment row load runs (48/80 divide
+    # into whole granules and 261 is host-padded, so neither reaches it)
+    b, h, nq, lk, d, dv = shape
+    q, k, v = _rand_qkv(b, h, nq, lk, d, dv, "cuda", seed=14)
+    qf = q.float().requires_grad_()
+    kf = k.float().requires_grad_()
+    vf = v.float().requires_grad_()
+    ref = _eager_ref(qf, kf, vf)
+    gout = torch.randn_like(ref)
+    ref.backward(gout)
+
+    qb, kb, vb = q.bfloat16(), k.bfloat16(), v.bfloat16()
+    out, lse = _ext().flash_fwd(qb, kb, vb, None, False, 0.0, 0)
+    assert torch.allclose(out.float(), ref.detach(), atol=2e-2, rtol=2e-2), \
+        f"max err {(out.float() - ref.detach()).abs().max().item()}"
+    grads = _ext().flash_bwd(gout.bfloat16(), qb, kb, vb, out, lse, None, False, 0.0, 0)
+    _assert_grads_close(grads, (qf.grad, kf.grad, vf.grad))
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_flash_bwd_pad_mask(causal):
+    b, h, nq, lk, d, dv = 2, 2, 40, 100, 32, 64
+    q, k, v = _rand_qkv(b, h, nq, lk, d, dv, "cuda", seed=15)
+    pad = torch.zeros(b, lk, dtype=torch.bool, device="cuda")
+    pad[0, 60:] = True
+    pad[1, :17] = True
+    qf = q.float().requires_grad_()
+    kf = k.float().requires_grad_()
+    vf = v.float().requires_grad_()
+    ref = _eager_ref(qf, kf, vf, pad_mask=pad, causal=causal)
+    gout = torch.randn_like(ref)
+    ref.backward(gout)
+
+    def run(kk, vv):
+        qb, kb, vb = q.bfloat16(), kk.bfloat16(), vv.bfloat16()
+        out, lse = _ext().flash_fwd(qb, kb, vb, pad, causal, 0.0, 0)
+        return _ext().flash_bwd(gout.bfloat16(), qb, kb, vb, out, lse, pad, causal, 0.0, 0)
+
+    dq, dk, dv_ = run(k, v)
+    _assert_grads_close((dq, dk, dv_), (qf.grad, kf.grad, vf.grad))
+
+    # padded key content must not matter, and padded keys get no gradient
+    k2, v2 = k.clone(), v.clone()
+    k2[0, :, 60:] = 7.0
+    v2[0, :, 60:] = -3.0
+    k2[1, :, :17] = 7.0
+    v2[1, :, :17] = -3.0
+    dq2, dk2, dv2 = run(k2, v2)
+    assert torch.allclose(dq.float(), dq2.float(), atol=1e-5)
+    for g in (dk, dv_, dk2, dv2):
+        assert torch.count_nonzero(g[0, :, 60:]) == 0
+        assert torch.count_nonzero(g[1, :, :17]) == 0
+
+
+@pytest.mark.parametrize("nq", [32, 128])  # v3 forward / pipelined forward
+def test_flash_dropout_bwd_matches_eager_with_fwd_mask(nq):
+    """The backward kernels regenerate the mask the forward drew: recover the
+    forward's kept mask with the identity-V probe, build the eager fp32
+    softmax(S) * mask / (1 - p) @ V under autograd, compare flash_bwd to it."""
+    b, h, lk, d = 1, 1, 64, 32
+    dv = lk
+    q, k, v = _rand_qkv(b, h, nq, lk, d, dv, "cuda", seed=16)
+    qb, kb, vb = q.bfloat16(), k.bfloat16(), v.bfloat16()
+    p, seed = 0.25, 777
+    v_eye = torch.eye(lk, device="cuda").expand(b, h, lk, lk).contiguous().bfloat16()
+    probs_dropped, _ = _ext().flash_fwd(qb, kb, v_eye, None, False, p, seed)
+    probs_full, _ = _ext().flash_fwd(qb, kb, v_eye, None, False, 0.0, 0)
+    mask = (probs_dropped.float() > 0) | (probs_full.float() == 0)
+    keep_rate = mask.float().mean().item()
+    assert abs(keep_rate - (1 - p)) < 0.05, keep_rate
+
+    qf = q.float().requires_grad_()
+    kf = k.float().requires_grad_()
+    vf = v.float().requires_grad_()
+    probs = torch.matmul(qf, kf.transpose(-2, -1)).softmax(dim=-1)
+    ref = torch.matmul(probs * mask.float() / (1 - p), vf)
+    gout = torch.randn_like(ref)
+    ref.backward(gout)
+
+    out, lse = _ext().flash_fwd(qb, kb, vb, None, False, p, seed)
+    assert torch.allclose(out.float(), ref.detach(), atol=2e-2, rtol=2e-2), \
+        f"max err {(out.float() - ref.detach()).abs().max().item()}"
+    grads = _ext().flash_bwd(gout.bfloat16(), qb, kb, vb, out, lse, None, False, p, seed)
+    _assert_grads_close(grads, (qf.grad, kf.grad, vf.grad))
