@@ -30,6 +30,9 @@ std::vector<torch::Tensor> gemm_bt_gelu_bf16(torch::Tensor x, torch::Tensor w,
                                              c10::optional<torch::Tensor> bias);
 bool gemm_bt_applicable(long M, long N, long K);
 torch::Tensor transpose_bf16(torch::Tensor x);
+std::vector<torch::Tensor> gemm_wgrad(torch::Tensor dy, torch::Tensor x, bool want_db);
+bool gemm_wgrad_applicable(long M, long N, long K);
+std::tuple<int64_t, int64_t, int64_t, int64_t> wgrad_plan(int64_t M, int64_t N, int64_t K);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_fwd", &gelu_bias_fwd, "fused bias+GELU forward (bf16)");
@@ -59,4 +62,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_bt_applicable", [](int64_t M, int64_t N, int64_t K) {
         return gemm_bt_applicable(M, N, K);
     }, "shape gate for the custom GEMM");
+    m.def("gemm_wgrad", &gemm_wgrad,
+          "split-K weight gradient dy^T @ x with fused bias-gradient sums: returns (dw[, db])");
+    m.def("gemm_wgrad_applicable", [](int64_t M, int64_t N, int64_t K) {
+        return gemm_wgrad_applicable(M, N, K);
+    }, "shape gate for the weight-gradient GEMM");
+    m.def("wgrad_plan", &wgrad_plan,
+          "host-only: (tile_n, tile_k, nsplit, rows_per_split) of the weight-gradient GEMM");
 }

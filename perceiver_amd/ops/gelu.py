@@ -60,10 +60,10 @@ class LinearGeluBias(torch.autograd.Function):
             from perceiver_amd.ops.linear import dgrad_matmul
 
             dx = dgrad_matmul(dpre, weight, dy.shape[:-1])
-        if ctx.needs_input_grad[1]:
-            dw = dpre.t().matmul(x2)
-        if ctx.needs_input_grad[2]:
-            db = _colsum(dpre)
+        from perceiver_amd.ops.linear import wgrad_and_bias
+
+        dw, db = wgrad_and_bias(dpre, x2, ctx.needs_input_grad[1], ctx.needs_input_grad[2],
+                                _colsum)
         return dx, dw, db
 
 

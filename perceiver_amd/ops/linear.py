@@ -9,9 +9,12 @@ data-gradient GEMM route through the deep-pipeline CDNA4 kernel
 (ops/csrc/gemm_bt.hip) when the shape matches its tiling — both operands of
 ``y = x @ w^T`` are K-contiguous in nn.Linear's native layout, and the dgrad
 ``dx = dy @ w`` reuses the same kernel with a (cheap, 2-4 MB) transposed
-weight copy. ``dw`` stays on hipBLASLt through torch.matmul.
+weight copy. The weight gradient ``dw = dy^T @ x`` and the bias gradient come
+from one split-K kernel (ops/csrc/gemm_wgrad.hip) on the shapes it accepts;
+elsewhere ``dw`` stays on hipBLASLt through torch.matmul.
 
 Set PERCEIVER_NO_CUSTOM_GEMM=1 to keep every GEMM on hipBLASLt (A/B lever).
+Set PERCEIVER_WGRAD=0 to restore ``dy.t() @ x`` plus the column-sum kernel.
 """
 from __future__ import annotations
 
@@ -32,6 +35,10 @@ _NO_CUSTOM_GEMM = os.environ.get("PERCEIVER_NO_CUSTOM_GEMM", "") == "1"
 # (ops/gelu.py LinearGeluBias), which stays on by default.
 _GEMM_FWD = os.environ.get("PERCEIVER_GEMM_FWD", "0") == "1" and not _NO_CUSTOM_GEMM
 _GEMM_DGRAD = os.environ.get("PERCEIVER_GEMM_DGRAD", "0") == "1" and not _NO_CUSTOM_GEMM
+# Weight gradients: the tuned library runs the NT orientation (both operands
+# strided along the reduction) at under half its forward rate, and the bias
+# gradient re-reads dy; gemm_wgrad does both in one pass.
+_WGRAD = os.environ.get("PERCEIVER_WGRAD", "1") != "0" and not _NO_CUSTOM_GEMM
 
 
 def _gemm_bt_ok(M: int, N: int, K: int) -> bool:
@@ -49,6 +56,22 @@ def dgrad_matmul(d2, weight, lead_shape):
     else:
         dx = d2.matmul(weight)
     return dx.view(*lead_shape, K)
+
+
+def wgrad_and_bias(d2, x2, need_dw: bool, need_db: bool, colsum):
+    """(dw, db) for a 2-D upstream grad d2 (M, N) and input x2 (M, K); either
+    is None when not needed. One gemm_wgrad call yields both on the shapes
+    the kernel accepts; otherwise ``d2.t() @ x2`` and ``colsum(d2)``."""
+    dw = db = None
+    if need_dw and _WGRAD and d2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 \
+            and hip.ext().gemm_wgrad_applicable(d2.shape[0], d2.shape[1], x2.shape[1]):
+        out = hip.ext().gemm_wgrad(d2, x2, need_db)
+        return out[0], (out[1] if need_db else None)
+    if need_dw:
+        dw = d2.t().matmul(x2)
+    if need_db:
+        db = colsum(d2)
+    return dw, db
 
 
 def _transposed(weight: torch.Tensor) -> torch.Tensor:
@@ -81,10 +104,9 @@ class _ColsumLinearFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = dgrad_matmul(dy2, weight, dy.shape[:-1])
-        if ctx.needs_input_grad[1]:
-            dw = dy2.t().matmul(x.reshape(-1, x.shape[-1]))
-        if ctx.needs_input_grad[2]:
-            db = hip.ext().colsum_bf16(dy2).to(dy.dtype)
+        dw, db = wgrad_and_bias(
+            dy2, x.reshape(-1, x.shape[-1]), ctx.needs_input_grad[1], ctx.needs_input_grad[2],
+            lambda d: hip.ext().colsum_bf16(d).to(dy.dtype))
         return dx, dw, db
 
 

@@ -1,7 +1,8 @@
 """Microbench: custom deep-pipeline GEMM vs hipBLASLt (F.linear) on the
 flagship projection shapes. Run on a GPU box:
     python tools/bench_gemm.py
-Prints TF/s for both paths per shape.
+Prints TF/s for both paths per shape, then the dgrad and the weight-gradient
+comparisons (`--wgrad-only` prints the last alone).
 """
 import pathlib
 import sys
@@ -12,6 +13,9 @@ import torch
 import torch.nn.functional as F
 
 from perceiver_amd.ops import hip as hip_ops
+from perceiver_amd.utils.tunableop import arm_tunableop
+
+arm_tunableop()  # before the first GEMM: the library side is the tuned one
 
 
 def bench(fn, iters=50, warmup=10):
@@ -28,9 +32,52 @@ def bench(fn, iters=50, warmup=10):
     return start.elapsed_time(end) / iters  # ms
 
 
+# (M, N, K): dw is (N, K), the reduction runs over M. MLM flagship first, then
+# the CLM / image / flow classes that pass the same gate.
+WGRAD_SHAPES = [
+    (16384, 1280, 1280), (16384, 1792, 1280), (16384, 256, 1280), (16384, 768, 1280),
+    (65536, 1280, 768), (65536, 768, 768), (65536, 256, 768),
+    (12288, 512, 512), (12288, 1536, 512), (12288, 2048, 512), (12288, 512, 2048),
+    (55296, 512, 512), (8192, 256, 256),
+]
+
+
+def bench_wgrad(ext, dev):
+    """dy.t() @ x plus colsum_bf16 (the tuned library path) versus one
+    gemm_wgrad call producing both dw and db."""
+    print("-- wgrad (dw = dy^T @ x, db = colsum(dy)) --")
+    for M, N, K in WGRAD_SHAPES:
+        dy = torch.randn(M, N, device=dev, dtype=torch.bfloat16)
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16) * 0.05
+        flops = 2.0 * M * N * K
+
+        def lib():
+            return dy.t().matmul(x), ext.colsum_bf16(dy)
+
+        t_mm = bench(lambda: dy.t().matmul(x))
+        t_lib = bench(lib)
+        if not ext.gemm_wgrad_applicable(M, N, K):
+            print(f"M={M} N={N} K={K}: matmul {t_mm:.3f} ms, +colsum {t_lib:.3f} ms | gemm_wgrad n/a")
+            continue
+        dw, db = ext.gemm_wgrad(dy, x, True)
+        ref = (dy.float().t() @ x.float()).to(torch.bfloat16)
+        match = (dw == ref).float().mean().item()
+        db_err = (db.float() - dy.float().sum(0)).abs().max().item()
+        t_new = bench(lambda: ext.gemm_wgrad(dy, x, True))
+        t_nodb = bench(lambda: ext.gemm_wgrad(dy, x, False))
+        plan = tuple(ext.wgrad_plan(M, N, K))
+        print(f"M={M} N={N} K={K}: matmul {t_mm:.3f} ms ({flops/(t_mm*1e9):.0f} TF/s), "
+              f"+colsum {t_lib:.3f} ms | gemm_wgrad {t_new:.3f} ms ({flops/(t_new*1e9):.0f} TF/s), "
+              f"no db {t_nodb:.3f} ms | speedup {t_lib/t_new:.2f}x | plan {plan} | "
+              f"exact-match {match:.4f} | db max err {db_err:.3f}")
+
+
 def main():
     ext = hip_ops.ext()
     dev = torch.device("cuda")
+    if "--wgrad-only" in sys.argv:
+        bench_wgrad(ext, dev)
+        return
     shapes = [
         (16384, 1280, 1280),   # MLM self-attn q/k/v/o and MLP
         (16384, 256, 1280),    # encoder CA q
@@ -76,6 +123,8 @@ def main():
             print(f"M={M} N={N} K={K}: torch-NN {t_nn:.3f} ms ({flops/(t_nn*1e9):.0f} TF/s) | "
                   f"gemm_bt+T {t_bt:.3f} ms ({flops/(t_bt*1e9):.0f} TF/s) | "
                   f"speedup {t_nn/t_bt:.2f}x | exact-match {match:.4f}")
+
+    bench_wgrad(ext, dev)
 
 
 if __name__ == "__main__":
