@@ -4,7 +4,6 @@
 //   m = lerp(m, g, 1-b1); v = b2*v + (1-b2)*g^2
 //   master = master*(1 - lr*wd) - lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
 // float4-vectorized, grid-stride, ~2048 blocks (guideline 11).
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
 
@@ -57,8 +56,7 @@ void adamw_step(torch::Tensor master, torch::Tensor m, torch::Tensor v, torch::T
     float inv_bc2 = 1.0f / sqrtf(1.0f - powf((float)beta2, (float)step));
     float wd_factor = 1.0f - (float)(lr * weight_decay);
     int threads = 256;
-    long blocks = std::max<long>(1, std::min<long>((n / 4 + threads - 1) / threads, 2048));
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(threads), 0,
+    hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_blocks(n / 4, threads, 2048)), dim3(threads), 0,
                        at::cuda::getCurrentCUDAStream(),
                        master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                        g.data_ptr<float>(), n, (float)lr, (float)beta1, (float)beta2,

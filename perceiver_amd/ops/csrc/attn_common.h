@@ -4,12 +4,7 @@
 // mapping, and the host-side launch planning. Each piece is defined once here.
 #pragma once
 
-#include <torch/extension.h>
-#include <algorithm>
 #include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 // ---- 16-lane row reductions (C-layout rows live in 16-lane groups) ----
 DEVINL float warp16_max(float x) {
@@ -64,19 +59,6 @@ DEVINL bf16x8 read_frag_tr16(const char* lds, int sub, int row0, int hi4, int lo
 #pragma unroll
     for (int e = 0; e < 4; ++e) { out[e] = lo[e]; out[e + 4] = hi[e]; }
     return out;
-}
-
-// 8 channels c0..c0+7 of a global row of d channels, zero past d: one 16-B
-// load for a full granule, element-wise on the ragged last one
-DEVINL short8v load_granule_guarded(const unsigned short* __restrict__ row, int c0, int d) {
-    short8v val = {};
-    if (c0 + 8 <= d) {
-        val = *reinterpret_cast<const short8v*>(row + c0);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) val[e] = (c0 + e < d) ? (short)row[c0 + e] : (short)0;
-    }
-    return val;
 }
 
 // Guarded staging: (ROWS_TILE x d) bf16 tile from global (row stride src_stride
@@ -225,19 +207,6 @@ inline bool pads_to_288(long D, long Dv) {
     return D > 160 && (D != 288 || Dv != 288) && D <= 288 && Dv <= 288;
 }
 
-// Dynamic-LDS requests above the 64 KiB default need a per-kernel opt-in
-// (the CU has 160 KiB).
-template <auto Kernel>
-inline void allow_dynamic_lds(size_t smem) {
-    if (smem <= 65536) return;
-    static bool raised = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return true;
-    }();
-    (void)raised;
-}
-
 // (B, H, N, last) view of freshly allocated merged-heads (B, N, H, last)
 // memory, for a result shaped like t (B, H, N, *): the module's head-merge
 // transpose+reshape after attention then costs nothing.
@@ -246,7 +215,7 @@ inline torch::Tensor empty_merged_heads(const torch::Tensor& t, long last) {
 }
 
 inline const bool* pad_mask_ptr(const c10::optional<torch::Tensor>& pad_mask) {
-    return (pad_mask.has_value() && pad_mask->defined()) ? pad_mask->data_ptr<bool>() : nullptr;
+    return has_tensor(pad_mask) ? pad_mask->data_ptr<bool>() : nullptr;
 }
 
 // ---- the deep-pipelined forward's entry points (flash_fwd_pipe.hip) ----

@@ -8,22 +8,18 @@
 // throttled how many blocks could be worth launching. Final shape: each WAVE
 // owns whole rows (grid-stride), accumulates per-lane fp32 partials in
 // registers, and writes its OWN partial row — no LDS, no atomics, no
-// barrier. The slab is tiled [c>>6][part][c&63] so the finalize kernel
-// streams 256-B bursts (the row-major slab cost it 16-32x DRAM
-// amplification reading 4-B columns at a 4*C stride).
-#include <torch/extension.h>
+// barrier. The slab is tiled for the finalize kernel (slab_index in
+// row_common.h).
 #include <ATen/cuda/CUDAContext.h>
-#include "common.h"
+#include "row_common.h"
 
 namespace {
 
-constexpr int LANES = 64;
 constexpr int WPB = 4;       // waves per block
-constexpr int CS_MAXC = 2048;
 
 // CHUNKS = ceil(C / 512); lane covers 8 contiguous elems per chunk.
 template <int CHUNKS>
-__launch_bounds__(LANES* WPB, CHUNKS >= 3 ? 2 : 4)
+__launch_bounds__(64 * WPB, CHUNKS >= 3 ? 2 : 4)
 __global__ void colsum_partial_kernel(const unsigned short* __restrict__ x,
                                       float* __restrict__ partial,
                                       long rows, int C) {
@@ -55,15 +51,13 @@ __global__ void colsum_partial_kernel(const unsigned short* __restrict__ x,
         }
     }
 
-    // wave-private tiled partial row; whole-granule stores per chunk
+    // wave-private tiled partial row
 #pragma unroll
     for (int i = 0; i < CHUNKS; ++i) {
-        int c0 = lane * 8 + i * 512;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            int c = c0 + e;
-            if (c < C)
-                partial[((long)(c >> 6) * nparts + wave0) * LANES + (c & 63)] = acc[i][e];
+            int c = granule_col(lane, i) + e;
+            if (c < C) partial[slab_index(c, wave0, nparts)] = acc[i][e];
         }
     }
 }
@@ -79,15 +73,16 @@ template <bool OUT_BF16>
 __global__ void colsum_finalize_kernel(const float* __restrict__ partial,
                                        void* __restrict__ out,
                                        int nparts, int C) {
-    const float* grp = partial + (long)blockIdx.x * nparts * LANES;
+    // column group blockIdx.x of the slab (slab_index), walked by pointer
+    const float* grp = partial + (long)blockIdx.x * nparts * SLAB_LANES;
     float acc = 0.f;
 #pragma unroll 8
     for (int p = threadIdx.y; p < nparts; p += FIN_ROWS)
-        acc += grp[(long)p * LANES + threadIdx.x];
-    __shared__ float red[FIN_ROWS][LANES];
+        acc += grp[(long)p * SLAB_LANES + threadIdx.x];
+    __shared__ float red[FIN_ROWS][SLAB_LANES];
     red[threadIdx.y][threadIdx.x] = acc;
     __syncthreads();
-    int c = blockIdx.x * LANES + threadIdx.x;
+    int c = blockIdx.x * SLAB_LANES + threadIdx.x;
     if (threadIdx.y == 0 && c < C) {
         float total = red[0][threadIdx.x];
 #pragma unroll
@@ -103,15 +98,11 @@ __global__ void colsum_finalize_kernel(const float* __restrict__ partial,
 
 void colsum_reduce_partials(const torch::Tensor& partial, torch::Tensor& out,
                             int nparts, int C) {
-    dim3 block(LANES, FIN_ROWS);
-    if (out.scalar_type() == torch::kBFloat16)
-        hipLaunchKernelGGL((colsum_finalize_kernel<true>), dim3((C + LANES - 1) / LANES),
-                           block, 0, at::cuda::getCurrentCUDAStream(),
-                           partial.data_ptr<float>(), out.data_ptr(), nparts, C);
-    else
-        hipLaunchKernelGGL((colsum_finalize_kernel<false>), dim3((C + LANES - 1) / LANES),
-                           block, 0, at::cuda::getCurrentCUDAStream(),
-                           partial.data_ptr<float>(), out.data_ptr(), nparts, C);
+    auto finalize = out.scalar_type() == torch::kBFloat16 ? colsum_finalize_kernel<true>
+                                                          : colsum_finalize_kernel<false>;
+    hipLaunchKernelGGL(finalize, dim3(slab_groups(C)), dim3(SLAB_LANES, FIN_ROWS), 0,
+                       at::cuda::getCurrentCUDAStream(), partial.data_ptr<float>(),
+                       out.data_ptr(), nparts, C);
     HIP_CHECK_LAST();
 }
 
@@ -120,36 +111,17 @@ torch::Tensor colsum_bf16(torch::Tensor x) {
     x = x.contiguous();
     long rows = x.size(0);
     int C = x.size(1);
-    TORCH_CHECK(C <= CS_MAXC, "colsum_bf16: C must be <= 2048");
+    TORCH_CHECK(C <= ROW_MAXC, "colsum_bf16: C must be <= 2048");
     if (rows == 0) return torch::zeros({(long)C}, x.options());
-    static const long kRedBlocks = [] {
-        const char* e = getenv("PERCEIVER_RED_BLOCKS");
-        return e ? atol(e) : 1024L;
-    }();
-    // row-adaptive block count (measured: 512 best for <=32k rows, 1024 for
-    // 64k+; more blocks shrink rows/wave until latency dominates)
-    long nblocks = std::min(std::max(rows / 32, (long)256), kRedBlocks);
-    nblocks = std::min(nblocks, (rows + WPB - 1) / WPB);
+    long nblocks = reduction_blocks(rows, WPB);
     long nparts = nblocks * WPB;  // one partial row per WAVE
-    long cgroups = (C + LANES - 1) / LANES;
-    auto partial = torch::empty({cgroups * nparts, (long)LANES},
-                                x.options().dtype(torch::kFloat32));
+    auto partial = empty_slab(x, C, nparts);
     auto out = torch::empty({(long)C}, x.options());  // bf16, rounded in-kernel
-    const unsigned short* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-    auto stream = at::cuda::getCurrentCUDAStream();
-    int chunks = (C + 511) / 512;
-    if (chunks == 1)
-        hipLaunchKernelGGL((colsum_partial_kernel<1>), dim3(nblocks), dim3(LANES * WPB), 0,
-                           stream, xp, partial.data_ptr<float>(), rows, C);
-    else if (chunks == 2)
-        hipLaunchKernelGGL((colsum_partial_kernel<2>), dim3(nblocks), dim3(LANES * WPB), 0,
-                           stream, xp, partial.data_ptr<float>(), rows, C);
-    else if (chunks == 3)
-        hipLaunchKernelGGL((colsum_partial_kernel<3>), dim3(nblocks), dim3(LANES * WPB), 0,
-                           stream, xp, partial.data_ptr<float>(), rows, C);
-    else
-        hipLaunchKernelGGL((colsum_partial_kernel<4>), dim3(nblocks), dim3(LANES * WPB), 0,
-                           stream, xp, partial.data_ptr<float>(), rows, C);
+    dispatch_chunks(C, [&](auto chunks) {
+        hipLaunchKernelGGL((colsum_partial_kernel<decltype(chunks)::value>), dim3(nblocks),
+                           dim3(64 * WPB), 0, at::cuda::getCurrentCUDAStream(), bf16_ptr(x),
+                           partial.data_ptr<float>(), rows, C);
+    });
     HIP_CHECK_LAST();
     colsum_reduce_partials(partial, out, (int)nparts, C);
     return out;

@@ -1,7 +1,10 @@
 // Shared helpers for the perceiver_amd CDNA4 (gfx950) kernels.
 #pragma once
 
+#include <torch/extension.h>
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
 
 #define DEVINL __device__ __forceinline__
 
@@ -13,6 +16,8 @@ typedef __attribute__((ext_vector_type(4))) short short4v;
 typedef __attribute__((ext_vector_type(8))) short short8v;
 typedef __attribute__((ext_vector_type(4))) float float4v;
 typedef __attribute__((ext_vector_type(2))) float float2v;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 // bf16 <-> f32 on raw bits (round-to-nearest-even); avoids the hip_bf16 C++ API.
 DEVINL float bf2f(unsigned short b) {
@@ -98,6 +103,69 @@ DEVINL float gelu_grad_f(float x) {
     float cdf = 0.5f * (1.0f + erf_fast(x * kInvSqrt2));
     float pdf = kInvSqrt2Pi * __expf(-0.5f * x * x);
     return cdf + x * pdf;
+}
+
+// 8 channels c0..c0+7 of a global row of d channels, zero past d: one 16-B
+// load for a full granule, element-wise on the ragged last one
+DEVINL short8v load_granule_guarded(const unsigned short* __restrict__ row, int c0, int d) {
+    short8v val = {};
+    if (c0 + 8 <= d) {
+        val = *reinterpret_cast<const short8v*>(row + c0);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) val[e] = (c0 + e < d) ? (short)row[c0 + e] : (short)0;
+    }
+    return val;
+}
+
+// XCD-aware bijective block order for a 1-D grid of nwg workgroups: hardware
+// deals consecutive block ids round-robin over the 8 XCDs, so this hands each
+// XCD a contiguous run of logical ids and neighbouring tiles (which share
+// operand rows) meet in one L2.
+DEVINL int xcd_block_order(int bid, int nwg) {
+    int q = nwg / 8, r = nwg % 8;
+    int xcd = bid % 8, idx = bid / 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// ---- host side ----
+
+// raw bf16 bits of a tensor's storage, as the kernels take them
+inline unsigned short* bf16_ptr(const torch::Tensor& t) {
+    return reinterpret_cast<unsigned short*>(t.data_ptr());
+}
+
+inline bool has_tensor(const c10::optional<torch::Tensor>& t) {
+    return t.has_value() && t->defined();
+}
+
+// null when the optional tensor (a bias, usually) is absent
+inline const unsigned short* opt_bf16_ptr(const c10::optional<torch::Tensor>& t) {
+    return has_tensor(t) ? bf16_ptr(*t) : nullptr;
+}
+
+// integer tuning knob from the environment; callers cache it in a static
+inline long env_int(const char* name, long dflt) {
+    const char* e = getenv(name);
+    return e ? atol(e) : dflt;
+}
+
+// grid of a grid-stride elementwise kernel: one thread per item up to cap blocks
+inline long elementwise_blocks(long items, int threads, long cap) {
+    return std::max<long>(1, std::min((items + threads - 1) / threads, cap));
+}
+
+// Dynamic-LDS requests above the 64 KiB default need a per-kernel opt-in
+// (the CU has 160 KiB).
+template <auto Kernel>
+inline void allow_dynamic_lds(size_t smem) {
+    if (smem <= 65536) return;
+    static bool raised = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        return true;
+    }();
+    (void)raised;
 }
 
 #define HIP_CHECK_LAST()                                                            \

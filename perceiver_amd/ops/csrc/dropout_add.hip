@@ -8,7 +8,6 @@
 // one of residual, one write. The mask is never materialized — the backward
 // regenerates it from the same counter-hash RNG (seed, element index), so
 //   dx = keep ? dy/(1-p) : 0,   dresidual = dy (the incoming tensor, no copy).
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
 
@@ -65,12 +64,8 @@ torch::Tensor dropout_add_fwd(torch::Tensor x, torch::Tensor res, double p, int6
     TORCH_CHECK(x.numel() % 8 == 0, "dropout_add: numel must be a multiple of 8");
     auto out = torch::empty_like(x);
     long n8 = x.numel() / 8;
-    long blocks = std::min((n8 + 255) / 256, (long)2048);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(dropout_add_fwd_kernel, dim3(blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const unsigned short*>(x.data_ptr()),
-                       reinterpret_cast<const unsigned short*>(res.data_ptr()),
-                       reinterpret_cast<unsigned short*>(out.data_ptr()),
+    hipLaunchKernelGGL(dropout_add_fwd_kernel, dim3(elementwise_blocks(n8, 256, 2048)), dim3(256),
+                       0, at::cuda::getCurrentCUDAStream(), bf16_ptr(x), bf16_ptr(res), bf16_ptr(out),
                        n8, (float)p, 1.0f / (1.0f - (float)p), (unsigned long long)seed);
     HIP_CHECK_LAST();
     return out;
@@ -81,11 +76,8 @@ torch::Tensor dropout_add_bwd(torch::Tensor dy, double p, int64_t seed) {
     dy = dy.contiguous();
     auto dx = torch::empty_like(dy);
     long n8 = dy.numel() / 8;
-    long blocks = std::min((n8 + 255) / 256, (long)2048);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(dropout_add_bwd_kernel, dim3(blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const unsigned short*>(dy.data_ptr()),
-                       reinterpret_cast<unsigned short*>(dx.data_ptr()),
+    hipLaunchKernelGGL(dropout_add_bwd_kernel, dim3(elementwise_blocks(n8, 256, 2048)), dim3(256),
+                       0, at::cuda::getCurrentCUDAStream(), bf16_ptr(dy), bf16_ptr(dx),
                        n8, (float)p, 1.0f / (1.0f - (float)p), (unsigned long long)seed);
     HIP_CHECK_LAST();
     return dx;

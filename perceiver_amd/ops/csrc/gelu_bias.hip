@@ -5,7 +5,6 @@
 //   fwd:  y = gelu(x + b)          x: (rows, C) bf16, b: (C) bf16 or absent
 //   bwd:  dx = dy * gelu'(x + b)   (db falls out of a matmul-free column sum done
 //                                   by the caller on dx_pre when bias is present)
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
 
@@ -60,46 +59,33 @@ __global__ void gelu_bias_bwd_kernel_bf16(
 
 }  // namespace
 
-torch::Tensor gelu_bias_fwd(torch::Tensor x, c10::optional<torch::Tensor> bias) {
-    TORCH_CHECK(x.is_cuda() && x.is_contiguous());
-    TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "gelu_bias_fwd: bf16 only");
-    auto y = torch::empty_like(x);
+// shared host half: dy absent runs the forward, present the backward
+static torch::Tensor gelu_bias_run(const torch::Tensor& x, const c10::optional<torch::Tensor>& bias,
+                                   const torch::Tensor* dy, const char* name) {
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && (!dy || dy->is_contiguous()));
+    TORCH_CHECK(x.scalar_type() == torch::kBFloat16, name, ": bf16 only");
+    auto out = torch::empty_like(x);
     long total = x.numel();
     int C = x.size(-1);
     TORCH_CHECK(C % 8 == 0, "inner dim must be a multiple of 8");
-    const unsigned short* bptr = nullptr;
-    if (bias.has_value() && bias->defined()) {
-        TORCH_CHECK(bias->is_contiguous() && bias->numel() == C);
-        bptr = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-    }
-    int threads = 256;
-    long blocks = std::max<long>(1, std::min<long>((total / 8 + threads - 1) / threads, 2048));
-    hipLaunchKernelGGL(gelu_bias_fwd_kernel_bf16, dim3(blocks), dim3(threads), 0,
-                       at::cuda::getCurrentCUDAStream(),
-                       reinterpret_cast<const unsigned short*>(x.data_ptr()), bptr,
-                       reinterpret_cast<unsigned short*>(y.data_ptr()), total, C);
+    if (has_tensor(bias)) TORCH_CHECK(bias->is_contiguous() && bias->numel() == C);
+    const int threads = 256;
+    const dim3 grid(elementwise_blocks(total / 8, threads, 2048));
+    auto stream = at::cuda::getCurrentCUDAStream();
+    if (dy)
+        hipLaunchKernelGGL(gelu_bias_bwd_kernel_bf16, grid, dim3(threads), 0, stream, bf16_ptr(x),
+                           opt_bf16_ptr(bias), bf16_ptr(*dy), bf16_ptr(out), total, C);
+    else
+        hipLaunchKernelGGL(gelu_bias_fwd_kernel_bf16, grid, dim3(threads), 0, stream, bf16_ptr(x),
+                           opt_bf16_ptr(bias), bf16_ptr(out), total, C);
     HIP_CHECK_LAST();
-    return y;
+    return out;
+}
+
+torch::Tensor gelu_bias_fwd(torch::Tensor x, c10::optional<torch::Tensor> bias) {
+    return gelu_bias_run(x, bias, nullptr, "gelu_bias_fwd");
 }
 
 torch::Tensor gelu_bias_bwd(torch::Tensor x, c10::optional<torch::Tensor> bias, torch::Tensor dy) {
-    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous());
-    TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "gelu_bias_bwd: bf16 only");
-    auto dx = torch::empty_like(x);
-    long total = x.numel();
-    int C = x.size(-1);
-    TORCH_CHECK(C % 8 == 0, "inner dim must be a multiple of 8");
-    const unsigned short* bptr = nullptr;
-    if (bias.has_value() && bias->defined()) {
-        bptr = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-    }
-    int threads = 256;
-    long blocks = std::max<long>(1, std::min<long>((total / 8 + threads - 1) / threads, 2048));
-    hipLaunchKernelGGL(gelu_bias_bwd_kernel_bf16, dim3(blocks), dim3(threads), 0,
-                       at::cuda::getCurrentCUDAStream(),
-                       reinterpret_cast<const unsigned short*>(x.data_ptr()), bptr,
-                       reinterpret_cast<const unsigned short*>(dy.data_ptr()),
-                       reinterpret_cast<unsigned short*>(dx.data_ptr()), total, C);
-    HIP_CHECK_LAST();
-    return dx;
+    return gelu_bias_run(x, bias, &dy, "gelu_bias_bwd");
 }

@@ -34,11 +34,8 @@
 // B stage through the identical path — the B^T orientation is what makes the
 // deep pipeline this uniform, and it is the layout every Linear in the model
 // already has.
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 namespace {
 
@@ -145,13 +142,7 @@ __global__ void gemm_bt_kernel(const unsigned short* __restrict__ xp,   // (M,K)
 
     // XCD-aware bijective block swizzle: contiguous grid chunks per XCD so
     // neighboring tiles (sharing A rows / B cols) hit the same L2
-    int bid = blockIdx.x;
-    {
-        int nwg = gridDim.x;
-        int q = nwg / 8, r = nwg % 8;
-        int xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_block_order(blockIdx.x, gridDim.x);
     const int n_tiles_n = N / TBN;
     const int m0 = (bid / n_tiles_n) * BM;
     const int n0 = (bid % n_tiles_n) * TBN;
@@ -322,10 +313,7 @@ __global__ void gemm_bt_kernel(const unsigned short* __restrict__ xp,   // (M,K)
 // round wins; tie goes to the wider tile (fewer blocks, more B reuse).
 // PERCEIVER_GEMM_BN=128|160 forces a tile for A/B measurement.
 int pick_bn(long M, long N) {
-    static const int forced = [] {
-        const char* e = getenv("PERCEIVER_GEMM_BN");
-        return e ? atoi(e) : 0;
-    }();
+    static const int forced = (int)env_int("PERCEIVER_GEMM_BN", 0);
     if (forced == 128 || forced == 160) {
         if (N % forced == 0) return forced;
     }
@@ -337,6 +325,16 @@ int pick_bn(long M, long N) {
     long w160 = waste(160), w128 = waste(128);
     if (w160 <= w128) return 160;
     return 128;
+}
+
+template <int TBN, bool GELU>
+void launch_gemm_bt(const torch::Tensor& x, const torch::Tensor& w, const unsigned short* bias,
+                    torch::Tensor& y, unsigned short* yg, long M, long N, long K) {
+    constexpr size_t smem = 3 * (size_t)(A_BYTES + TBN * BK * 2);
+    allow_dynamic_lds<gemm_bt_kernel<TBN, GELU>>(smem);
+    hipLaunchKernelGGL((gemm_bt_kernel<TBN, GELU>), dim3((M / BM) * (N / TBN)), dim3(THREADS), smem,
+                       at::cuda::getCurrentCUDAStream(), bf16_ptr(x), bf16_ptr(w), bias,
+                       bf16_ptr(y), yg, (int)M, (int)N, (int)K);
 }
 
 }  // namespace
@@ -359,47 +357,20 @@ static std::vector<torch::Tensor> gemm_bt_run(torch::Tensor x, torch::Tensor w,
     TORCH_CHECK(gemm_bt_applicable(M, N, K), "gemm_bt: unsupported shape ", M, "x", N, "x", K);
     auto y = torch::empty({M, N}, x.options());
     torch::Tensor ygel;
-    unsigned short* ygp = nullptr;
-    if (with_gelu) {
-        ygel = torch::empty({M, N}, x.options());
-        ygp = reinterpret_cast<unsigned short*>(ygel.data_ptr());
-    }
-    const unsigned short* bp = nullptr;
-    torch::Tensor bc;
-    if (bias.has_value() && bias->defined()) {
-        bc = bias->contiguous();
-        TORCH_CHECK(bc.numel() == N && bc.scalar_type() == torch::kBFloat16);
-        bp = reinterpret_cast<const unsigned short*>(bc.data_ptr());
+    if (with_gelu) ygel = torch::empty({M, N}, x.options());
+    if (has_tensor(bias)) {
+        bias = bias->contiguous();
+        TORCH_CHECK(bias->numel() == N && bias->scalar_type() == torch::kBFloat16);
     }
     int bn = pick_bn(M, N);
-    static bool raised = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bt_kernel<128, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bt_kernel<128, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bt_kernel<160, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bt_kernel<160, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return true;
-    }();
-    (void)raised;
-    auto launch = [&](auto kern, int tbn) {
-        long grid = (M / BM) * (N / tbn);
-        size_t smem = 3 * (size_t)(A_BYTES + tbn * BK * 2);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), smem,
-                           at::cuda::getCurrentCUDAStream(),
-                           reinterpret_cast<const unsigned short*>(x.data_ptr()),
-                           reinterpret_cast<const unsigned short*>(wc.data_ptr()),
-                           bp, reinterpret_cast<unsigned short*>(y.data_ptr()),
-                           ygp, (int)M, (int)N, (int)K);
-    };
+    const unsigned short* bp = opt_bf16_ptr(bias);
+    unsigned short* ygp = with_gelu ? bf16_ptr(ygel) : nullptr;
     if (bn == 160) {
-        if (with_gelu) launch(gemm_bt_kernel<160, true>, 160);
-        else launch(gemm_bt_kernel<160, false>, 160);
+        if (with_gelu) launch_gemm_bt<160, true>(x, wc, bp, y, ygp, M, N, K);
+        else launch_gemm_bt<160, false>(x, wc, bp, y, ygp, M, N, K);
     } else {
-        if (with_gelu) launch(gemm_bt_kernel<128, true>, 128);
-        else launch(gemm_bt_kernel<128, false>, 128);
+        if (with_gelu) launch_gemm_bt<128, true>(x, wc, bp, y, ygp, M, N, K);
+        else launch_gemm_bt<128, false>(x, wc, bp, y, ygp, M, N, K);
     }
     HIP_CHECK_LAST();
     if (with_gelu) return {y, ygel};

@@ -29,9 +29,7 @@
 //   - a second small kernel sums the nsplit fp32 slabs in fixed order and
 //     rounds dw and db once. Deterministic, no atomics, no communication
 //     between workgroups inside a launch.
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
-#include <cstdlib>
 #include <tuple>
 #include "attn_common.h"
 
@@ -64,10 +62,7 @@ double plan_cost(long N, long K, int tile_k, long steps_per_split, long nsplit, 
 }
 
 int forced_tile_k() {
-    static const int forced = [] {
-        const char* e = getenv("PERCEIVER_WGRAD_TK");
-        return e ? atoi(e) : 0;
-    }();
+    static const int forced = (int)env_int("PERCEIVER_WGRAD_TK", 0);
     return forced;
 }
 
@@ -157,17 +152,9 @@ __global__ void gemm_wgrad_kernel(const unsigned short* __restrict__ dyp,  // (M
     const int wk = wid % WAVES_K;
     const int wn = wid / WAVES_K;
 
-    // XCD-aware bijective block order (as gemm_bt_kernel): blocks that share
-    // an XCD get a contiguous run of ids, and ids run tile-fastest inside a
-    // split, so the tiles of one split — which read the same dy and x rows —
-    // meet in one L2.
-    int bid = blockIdx.x;
-    {
-        int nwg = gridDim.x;
-        int q = nwg / 8, r = nwg % 8;
-        int xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // ids run tile-fastest inside a split, so in XCD order the tiles of one
+    // split — which read the same dy and x rows — meet in one L2
+    const int bid = xcd_block_order(blockIdx.x, gridDim.x);
     const int tiles_k = K / TK;
     const int tiles = (N / TN) * tiles_k;
     const int split = bid / tiles;
@@ -337,9 +324,7 @@ void launch_wgrad(const torch::Tensor& dy, const torch::Tensor& x, torch::Tensor
     allow_dynamic_lds<gemm_wgrad_kernel<TK, WANT_DB>>(smem);
     const long grid = (N / TN) * (K / TK) * p.nsplit;
     hipLaunchKernelGGL((gemm_wgrad_kernel<TK, WANT_DB>), dim3(grid), dim3(THREADS), smem,
-                       at::cuda::getCurrentCUDAStream(),
-                       reinterpret_cast<const unsigned short*>(dy.data_ptr()),
-                       reinterpret_cast<const unsigned short*>(x.data_ptr()),
+                       at::cuda::getCurrentCUDAStream(), bf16_ptr(dy), bf16_ptr(x),
                        slab.data_ptr<float>(), db_part, (int)M, (int)N, (int)K,
                        (int)p.rows_per_split);
 }
@@ -372,7 +357,7 @@ std::vector<torch::Tensor> gemm_wgrad(torch::Tensor dy, torch::Tensor x, bool wa
         db_part = torch::empty({(long)p.nsplit, N}, f32);
         db = torch::empty({N}, dy.options());
         db_part_p = db_part.data_ptr<float>();
-        db_p = reinterpret_cast<unsigned short*>(db.data_ptr());
+        db_p = bf16_ptr(db);
     }
     if (p.tile_k == 256) {
         if (want_db) launch_wgrad<256, true>(dy, x, slab, db_part_p, M, N, K, p);
@@ -387,8 +372,7 @@ std::vector<torch::Tensor> gemm_wgrad(torch::Tensor dy, torch::Tensor x, bool wa
     const int db_blocks = want_db ? (int)((N + 255) / 256) : 0;
     hipLaunchKernelGGL(gemm_wgrad_finalize_kernel, dim3(dw_blocks + db_blocks), dim3(256), 0,
                        at::cuda::getCurrentCUDAStream(), slab.data_ptr<float>(), db_part_p,
-                       reinterpret_cast<unsigned short*>(dw.data_ptr()), db_p, NK, (int)N,
-                       p.nsplit, dw_blocks);
+                       bf16_ptr(dw), db_p, NK, (int)N, p.nsplit, dw_blocks);
     HIP_CHECK_LAST();
     if (want_db) return {dw, db};
     return {dw};

@@ -13,7 +13,6 @@
 // batch/head/row strides (cached-KV strided views pass through uncopied).
 // The backward is the same rotation with sin negated (orthogonal transform),
 // so one kernel serves both directions via `neg_sin`.
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
 
@@ -76,12 +75,9 @@ torch::Tensor rotary_apply(torch::Tensor t, torch::Tensor frq, int64_t rot, bool
     if (t.numel() == 0) return out;
     long total = (long)B * H * N * ((D + 1) / 2);
     int threads = 256;
-    long blocks = std::min((total + threads - 1) / threads, (long)16384);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(rotary_kernel, dim3((unsigned)blocks), dim3(threads), 0, stream,
-                       reinterpret_cast<const unsigned short*>(t.data_ptr()),
-                       frq.data_ptr<float>(),
-                       reinterpret_cast<unsigned short*>(out.data_ptr()),
+    hipLaunchKernelGGL(rotary_kernel, dim3(elementwise_blocks(total, threads, 16384)), dim3(threads),
+                       0, at::cuda::getCurrentCUDAStream(), bf16_ptr(t), frq.data_ptr<float>(),
+                       bf16_ptr(out),
                        t.stride(0), t.stride(1), t.stride(2),
                        frq.size(0) > 1 ? frq.stride(0) : 0, frq.stride(1),
                        B, H, N, D, (int)rot, (int)neg_sin);

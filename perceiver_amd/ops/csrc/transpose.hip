@@ -6,7 +6,6 @@
 // sits on the critical path ~80 times per training step. Classic LDS-tiled
 // transpose: 64x64 tiles staged through padded LDS, 16-B coalesced loads on
 // the input side, 16-B coalesced stores on the output side.
-#include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
 
@@ -74,10 +73,7 @@ torch::Tensor transpose_bf16(torch::Tensor x) {
     auto out = torch::empty({K, N}, x.options());
     dim3 grid((N + TDIM - 1) / TDIM, (K + TDIM - 1) / TDIM);
     hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0,
-                       at::cuda::getCurrentCUDAStream(),
-                       reinterpret_cast<const unsigned short*>(x.data_ptr()),
-                       reinterpret_cast<unsigned short*>(out.data_ptr()),
-                       (int)N, (int)K);
+                       at::cuda::getCurrentCUDAStream(), bf16_ptr(x), bf16_ptr(out), (int)N, (int)K);
     HIP_CHECK_LAST();
     return out;
 }

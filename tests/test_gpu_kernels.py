@@ -170,8 +170,7 @@ def test_fused_layer_norm_matches_torch():
         w = torch.randn(C, device="cuda").abs() + 0.5
         b = torch.randn(C, device="cuda")
         ref = torch.nn.functional.layer_norm(x, (C,), w, b, 1e-5)
-        if C % 8:  # kernel requires the vector path; module falls back for others
-            continue
+        # C = 322 ends in a ragged granule: the kernel walks it element-wise
         y, mean, rstd = _ext().ln_fwd(x.bfloat16(), w.bfloat16(), b.bfloat16(), 1e-5)
         assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2), C
 
@@ -190,6 +189,41 @@ def test_fused_layer_norm_matches_torch():
             scale = want.abs().mean().clamp(min=1.0)
             err = (got - want).abs().max().item()
             assert err < 0.04 * float(scale) + 0.08, (C, err, float(scale))
+
+
+@pytest.mark.parametrize("rows,C", [
+    (37, 8),      # one granule; rows not a multiple of the 4 waves per block
+    (37, 322),    # the LayerNorm(322) case: ragged last granule, rows 4-byte aligned only
+    (37, 520),    # second chunk holds one granule
+    (37, 1030),   # three chunks, ragged
+    (37, 1540),   # four chunks, ragged
+    (3, 2048),    # four full chunks; fewer rows than waves in a block
+])
+def test_layer_norm_ragged_and_multichunk_rows(rows, C):
+    g = torch.Generator(device="cpu").manual_seed(rows * 4096 + C)
+    x = torch.randn(rows, C, generator=g).bfloat16().cuda()
+    w = (torch.randn(C, generator=g).abs() + 0.5).bfloat16().cuda()
+    b = torch.randn(C, generator=g).bfloat16().cuda()
+    dy = torch.randn(rows, C, generator=g).bfloat16().cuda()
+
+    xf = x.float().requires_grad_()
+    wf = w.float().requires_grad_()
+    bf = b.float().requires_grad_()
+    ref = torch.nn.functional.layer_norm(xf, (C,), wf, bf, 1e-5)
+    ref.backward(dy.float())
+
+    y, mean, rstd = _ext().ln_fwd(x, w, b, 1e-5)
+    assert torch.allclose(y.float(), ref.detach(), atol=3e-2, rtol=3e-2)
+    dx, dw, db = _ext().ln_bwd(dy, x, w, mean, rstd, True)
+    dx_only = _ext().ln_bwd(dy, x, w, mean, rstd, False)[0]
+    for got in (dx, dx_only):
+        assert got.shape == x.shape
+        assert torch.allclose(got.float(), xf.grad, atol=5e-2, rtol=5e-2)
+    for got, want in ((dw.float(), wf.grad), (db.float(), bf.grad)):
+        assert got.shape == want.shape
+        scale = want.abs().mean().clamp(min=1.0)
+        err = (got - want).abs().max().item()
+        assert err < 0.04 * float(scale) + 0.08, (err, float(scale))
 
 
 def test_layer_norm_module_dispatch():
@@ -290,7 +324,7 @@ def test_fused_adamw_matches_reference_adamw():
         optbf.step()
     for a, b in zip(p32, pbf):
         # params live in bf16: tolerance = ~2 bf16 ulps at |w|~2 (the fused kernel
-        # itself matches the fp32 update to ~2e-7; see tools/dbg_adamw.py)
+        # itself matches the fp32 update to ~2e-7)
         err = (a.detach() - b.detach().float()).abs().max().item()
         assert err < 4e-2, err
 
@@ -621,7 +655,9 @@ def test_colsum_matches_torch_sum():
     # the kernel emits bf16 directly (single final rounding, same as the old
     # fp32-out + .to(bf16) pair); compare against the identically-rounded
     # torch sum with tolerance for fp32 accumulation-order ulps
-    for rows, C in [(401408, 261), (16384, 1792), (1000, 7)]:
+    # (3, 2048): fewer rows than waves per block, so the block count clamps
+    # to one; (130, 1030): three chunks with a ragged tail
+    for rows, C in [(401408, 261), (16384, 1792), (1000, 7), (3, 2048), (130, 1030)]:
         x = (torch.randn(rows, C) * 0.5).bfloat16().cuda()
         got = _ext().colsum_bf16(x)
         assert got.dtype == torch.bfloat16
