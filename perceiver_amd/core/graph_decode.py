@@ -21,9 +21,16 @@ Design (vs. the host-driven path in ``PerceiverAR.forward``):
   device position counter through the model's own ``FrequencyPositionEncoding``,
   and for the self-attention stack written into the last row of the table
   (``right_align=True`` makes the 1-row query read exactly that row).
-- Greedy selection, the token round-trip and the output record
-  (``index_copy_`` at a device step counter) all stay on the GPU: a decode of N
-  tokens is N graph replays with zero host synchronisation.
+- Token selection (greedy, or temperature / top-k / top-p sampling), the EOS
+  fill and ``done`` mask, the token round-trip and the output record at a
+  device step counter are ONE launch of the ``decode_select`` kernel
+  (``ops/sample.py``), which reads every sampling parameter per row from device
+  buffers: one captured graph serves every sampling configuration, and
+  ``set_sampling`` rewrites the buffers between requests without a recapture.
+  The cache lengths, the step cursor and the draw index are views of one small
+  tensor that a single ``add_`` advances after the kernel, so no block of the
+  kernel races another on a counter. A decode of N tokens is N graph replays
+  with zero host synchronisation.
 
 The un-captured step (``_step``) runs eagerly on any device, which is what the
 CPU numerics test compares against the host-driven cached forward. The reference
@@ -35,6 +42,10 @@ from __future__ import annotations
 from typing import List, Optional
 
 import torch
+
+from perceiver_amd.ops import sample as _sample
+
+_KEEP = object()  # set_sampling: leave this parameter as it is
 
 from perceiver_amd.core.cache import StaticKVCache
 from perceiver_amd.core.position import RotaryPositionEmbedding
@@ -54,22 +65,26 @@ class GraphedDecoder:
 
     def __init__(self, model, caches: List[StaticKVCache], use_graph: bool = True,
                  do_sample: bool = False, temperature: float = 1.0,
-                 top_k: Optional[int] = None):
-        """``do_sample``: in-graph ancestral sampling (temperature scaling +
-        optional top-k truncation + exponential-race Gumbel trick). torch's CUDA
-        Philox state is graph-safe, so replays draw fresh randomness with zero
-        host round-trips, same as the greedy path."""
+                 top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None):
+        """``do_sample``: in-graph ancestral sampling (temperature scaling,
+        optional top-k and top-p truncation). On the GPU the selection is the
+        ``decode_select`` kernel with a counter-hash draw keyed by a per-prefill
+        seed and a device draw index, so replays draw fresh randomness with zero
+        host round-trips; elsewhere it is the torch composition on torch's RNG.
+        ``eos_token_id``: rows that emitted it keep emitting ``pad_token_id``
+        (EOS itself when None) and are flagged in ``finished``."""
         self.model = model
         self.caches = caches
-        self.do_sample = do_sample
-        self.temperature = temperature
-        self.top_k = top_k
         p = next(model.parameters())
         self.device, self.dtype = p.device, p.dtype
         self.use_graph = use_graph and p.device.type == "cuda"
         self.batch = caches[0].k_buf.shape[0]
         self.ca_cap = caches[0].capacity
         self.sa_cap = caches[1].capacity if len(caches) > 1 else 0
+        self.vocab = model.config.vocab_size
+        # decided once: a captured graph holds whichever selection it was built with
+        self.use_kernel = _sample.kernel_applicable(self.device, self.vocab)
 
         # full-capacity reads include not-yet-written rows: they are masked, but
         # 0-prob × garbage-NaN would still poison P@V — keep the tails finite
@@ -79,23 +94,91 @@ class GraphedDecoder:
 
         dev = self.device
         self.tok = torch.zeros(self.batch, 1, dtype=torch.long, device=dev)
-        # device counters: current cache lengths (= index the next token is
-        # written at) and the output-record cursor
-        self.ca_len = torch.zeros(1, dtype=torch.long, device=dev)
-        self.sa_len = torch.zeros(1, dtype=torch.long, device=dev)
-        self.step_idx = torch.zeros(1, dtype=torch.long, device=dev)
+        # device counters, views of ONE tensor so a single add_ advances them:
+        # current cache lengths (= index the next token is written at), the
+        # output-record cursor and the sampler's draw index
+        self.counters = torch.zeros(4, dtype=torch.long, device=dev)
+        self.ca_len = self.counters[0:1]
+        self.sa_len = self.counters[1:2]
+        self.step_idx = self.counters[2:3]
+        self.draw_idx = self.counters[3:4]
         self.ar_ca = torch.arange(self.ca_cap, device=dev).unsqueeze(0)
         self.ar_sa = torch.arange(self.sa_cap, device=dev).unsqueeze(0)
         self.out_buf = torch.zeros(self.batch, self.sa_cap or self.ca_cap,
                                    dtype=torch.long, device=dev)
+        # sampling parameters, per row, read by the kernel every step
+        self.p_do_sample = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+        self.p_temperature = torch.ones(self.batch, dtype=torch.float32, device=dev)
+        self.p_top_k = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+        self.p_top_p = torch.ones(self.batch, dtype=torch.float32, device=dev)
+        self.seed = torch.zeros(1, dtype=torch.long, device=dev)
+        self.eos_fill = torch.tensor([-1, 0], dtype=torch.long, device=dev)
+        self.done = torch.zeros(self.batch, dtype=torch.bool, device=dev)
+        self._generator = None
+        self._steps_host = 0
         self._graph = None
+        self.do_sample, self.temperature, self.top_k, self.top_p = False, 1.0, None, None
+        self.eos_token_id = self.pad_token_id = None
+        self.set_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k,
+                          top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id)
+
+    # ----------------------------------------------------------------- sampling
+
+    def set_sampling(self, do_sample=_KEEP, temperature=_KEEP, top_k=_KEEP, top_p=_KEEP,
+                     eos_token_id=_KEEP, pad_token_id=_KEEP):
+        """Rewrite the sampling parameters between requests. ``do_sample``,
+        ``temperature``, ``top_k`` and ``top_p`` take scalars or per-row
+        ``(batch,)`` tensors; None switches top-k / top-p / EOS off. With the
+        kernel the captured graph is reused as it is. The torch composition
+        bakes the values into the graph, so there a change drops the graph and
+        the next ``decode`` captures again."""
+        if do_sample is not _KEEP:
+            self.do_sample = do_sample
+        if temperature is not _KEEP:
+            self.temperature = temperature
+        if top_k is not _KEEP:
+            self.top_k = top_k
+        if top_p is not _KEEP:
+            self.top_p = top_p
+        if eos_token_id is not _KEEP:
+            self.eos_token_id = eos_token_id
+        if pad_token_id is not _KEEP:
+            self.pad_token_id = pad_token_id
+        for name, v in (("eos_token_id", self.eos_token_id), ("pad_token_id", self.pad_token_id)):
+            if v is not None and not 0 <= int(v) < self.vocab:
+                raise ValueError(f"{name}={v} outside the vocabulary [0, {self.vocab})")
+
+        B, dev = self.batch, self.device
+        self.p_do_sample.copy_(_sample.row_param(self.do_sample, B, torch.int32, dev, 0))
+        self.p_temperature.copy_(_sample.row_param(self.temperature, B, torch.float32, dev, 1.0))
+        self.p_top_k.copy_(_sample.row_param(self.top_k, B, torch.int32, dev, 0))
+        self.p_top_p.copy_(_sample.row_param(self.top_p, B, torch.float32, dev, 1.0))
+        eos = -1 if self.eos_token_id is None else int(self.eos_token_id)
+        fill = self.pad_token_id if self.pad_token_id is not None else self.eos_token_id
+        self._eos, self._fill = eos, 0 if fill is None else int(fill)
+        self.eos_fill.copy_(torch.tensor([self._eos, self._fill], dtype=torch.long))
+        ds = self.do_sample
+        self._any_sample = bool(ds.any()) if isinstance(ds, torch.Tensor) else bool(ds)
+        if not self.use_kernel:
+            self._graph = None
+
+    @property
+    def finished(self) -> torch.Tensor:
+        """(batch,) bool: rows that have emitted ``eos_token_id`` since the prefill."""
+        return self.done
 
     # ------------------------------------------------------------------ prefill
 
     @torch.no_grad()
-    def prefill(self, prompt: torch.Tensor, prefix_len: int) -> torch.Tensor:
+    def prefill(self, prompt: torch.Tensor, prefix_len: int,
+                generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """Run the normal host-driven cached forward over the prompt, seed the
-        device counters/buffers, and return the first greedy token."""
+        device counters/buffers, and return the first selected token.
+
+        Sampling draws a fresh seed here, from ``generator`` when given and
+        otherwise from torch's global generator, and restarts the draw index:
+        equally seeded generators decode identical samples, and two prefills
+        without one decode different samples."""
         for c in self.caches:
             c.disable_graph_append()
             c.reset()
@@ -103,34 +186,74 @@ class GraphedDecoder:
             # step then never touches cached rows again (no O(cache) re-rotate)
             c.pre_rotated = True
         out = self.model(prompt, prefix_len=prefix_len, kv_cache=self.caches)
-        tok = self._select(out.logits[:, -1, :].float())
 
         n0 = prompt.shape[1]
         prefix0 = prefix_len
-        self.tok.copy_(tok)
         self.ca_len.fill_(n0)
         self.sa_len.fill_(n0 - prefix0)
         self.step_idx.fill_(0)
+        self.draw_idx.fill_(0)
+        self.done.zero_()
+        self._generator = None if self.use_kernel else generator  # torch composition only
+        if self.use_kernel:
+            if self._any_sample:  # greedy draws nothing
+                gdev = generator.device if generator is not None else "cpu"
+                self.seed.fill_(int(torch.randint(0, 2 ** 62, (1,), generator=generator,
+                                                  device=gdev).item()))
+        elif generator is not None and self.use_graph and self._any_sample:
+            raise RuntimeError("a generator on the captured-graph path needs the decode_select "
+                               "kernel (PERCEIVER_DECODE_SELECT=0 or an unsupported vocabulary)")
+        self._select_into_tok(out.logits[:, -1, :], record=False)
+        self.draw_idx.fill_(1)
+
         self.ca_len_host = n0
         self.sa_len_host = n0 - prefix0
+        self._steps_host = 0
         self.caches[0].enable_graph_append(self.ca_len)
         for c in self.caches[1:]:
             c.enable_graph_append(self.sa_len)
-        return tok
+        return self.tok.clone()
+
+    def _select_into_tok(self, logits: torch.Tensor, record: bool):
+        """tok <- next token from (batch, vocab) logits, with the EOS fill and
+        ``done`` update; ``record`` first stores the previous token at the step
+        cursor of ``out_buf``. One kernel launch on the GPU."""
+        if self.use_kernel:
+            from perceiver_amd.ops import hip
+
+            hip.ext().decode_select(
+                logits, self.p_do_sample, self.p_temperature, self.p_top_k, self.p_top_p,
+                self.seed, self.draw_idx, tok=self.tok.view(-1),
+                out_buf=self.out_buf if record else None,
+                step=self.step_idx if record else None,
+                done=self.done, eos_fill=self.eos_fill)
+            return
+        if record:
+            self.out_buf.index_copy_(1, self.step_idx, self.tok)
+        tok = self._select(logits.float())
+        if self.eos_token_id is not None:
+            tok = torch.where(self.done[:, None], torch.full_like(tok, self._fill), tok)
+            self.done.logical_or_(tok.squeeze(-1) == self._eos)
+        self.tok.copy_(tok)
 
     def _select(self, scores: torch.Tensor) -> torch.Tensor:
-        """Greedy or Gumbel-max sampled token from (batch, vocab) fp32 scores.
+        """Greedy or Gumbel-max sampled token from (batch, vocab) fp32 scores:
+        the torch composition, used off the GPU and as the A/B reference.
         Capture-safe: torch's CUDA Philox state is graph-aware, and the
         exponential_/log Gumbel trick avoids multinomial's sync."""
-        if not self.do_sample:
-            return scores.argmax(-1, keepdim=True)
-        if self.temperature != 1.0:
-            scores = scores / self.temperature
-        if self.top_k is not None and self.top_k > 0:
-            kth = torch.topk(scores, min(self.top_k, scores.shape[-1]))[0][..., -1, None]
-            scores = scores.masked_fill(scores < kth, float("-inf"))
-        g = torch.empty_like(scores).exponential_().log().neg_()
-        return (scores + g).argmax(-1, keepdim=True)
+        greedy = scores.argmax(-1, keepdim=True)
+        if not self._any_sample:
+            return greedy
+        T = _sample.row_param(self.temperature, self.batch, torch.float32, scores.device, 1.0)
+        scaled = scores / T[:, None]
+        if self.top_k is not None or self.top_p is not None:
+            keep = _sample.keep_mask_reference(scores, T, self.top_k, self.top_p)
+            scaled = scaled.masked_fill(~keep, float("-inf"))
+        g = torch.empty_like(scaled).exponential_(generator=self._generator).log().neg_()
+        drawn = (scaled + g).argmax(-1, keepdim=True)
+        if isinstance(self.do_sample, torch.Tensor):
+            return torch.where(self.p_do_sample[:, None] != 0, drawn, greedy)
+        return drawn
 
     # --------------------------------------------------------------------- step
 
@@ -174,11 +297,8 @@ class GraphedDecoder:
 
         # token selection + bookkeeping, all on-device: the graph is self-advancing
         self.last_logits = logits  # graph-pool tensor: valid until the next replay
-        self.out_buf.index_copy_(1, self.step_idx, self.tok)
-        self.tok.copy_(self._select(logits[:, -1, :].float()))
-        self.ca_len.add_(1)
-        self.sa_len.add_(1)
-        self.step_idx.add_(1)
+        self._select_into_tok(logits[:, -1, :], record=True)
+        self.counters.add_(1)  # cache lengths, step cursor and draw index together
 
     def _capture(self):
         s = torch.cuda.Stream()
@@ -195,9 +315,13 @@ class GraphedDecoder:
 
     @torch.no_grad()
     def decode(self, n: int) -> torch.Tensor:
-        """Generate ``n`` greedy tokens after ``prefill``; returns (batch, n).
-        The first call captures the step graph (2 warmup steps run eagerly and
-        count toward ``n``); later calls are pure replays."""
+        """Generate the next ``n`` tokens after ``prefill``; returns (batch, n).
+        May be called repeatedly after one prefill (``generate`` decodes in
+        chunks to look at ``finished`` in between). The first call captures the
+        step graph (2 warmup steps run eagerly and count toward ``n``); later
+        calls are pure replays."""
+        if n < 1:
+            raise ValueError("decode() needs n >= 1")
         if self.ca_len_host + n > self.ca_cap or self.sa_len_host + n > self.sa_cap:
             raise RuntimeError("decode would overflow the KV cache capacity")
         done = 0
@@ -217,5 +341,7 @@ class GraphedDecoder:
         # row i is the token fed INTO step i, i.e. the model's (i)'th generated
         # token counting the prefill argmax as the 0'th. Together with the final
         # self.tok this yields the n generated tokens after the prefill token.
-        first = self.out_buf[:, 1:n]
+        s0 = self._steps_host
+        self._steps_host += n
+        first = self.out_buf[:, s0 + 1:s0 + n]
         return torch.cat([first, self.tok], dim=1)

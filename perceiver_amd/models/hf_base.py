@@ -288,14 +288,29 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
 
             # hipGraph fast path: when every generated token stays within the
             # latent-growth phase of the schedule (no prefix growth/window
-            # slide), no EOS cut-off is requested, and the sampling mode is
-            # graph-expressible, decode is one captured-graph replay per token.
-            # Decoders (captured graph + caches) are cached per batch/sampling
-            # config — repeated serving requests only pay prefill + replays.
-            # Weight updates are fine (the graph holds parameter pointers).
-            if (p.device.type == "cuda" and eos_token_id is None
+            # slide), decode is one captured-graph replay per token. Token
+            # selection is the decode_select kernel, which reads temperature,
+            # top-k, top-p, EOS and the seed from device buffers: greedy,
+            # sampled, nucleus, EOS-stopped and seeded requests all replay the
+            # same graph. Decoders (captured graph + caches) are cached per
+            # batch size — repeated serving requests only pay prefill +
+            # replays. Weight updates are fine (the graph holds parameter
+            # pointers). Without the kernel (PERCEIVER_DECODE_SELECT=0, or a
+            # vocabulary it has no tier for) the torch selection bakes its
+            # parameters into the graph, and top-p, EOS and generator requests
+            # take the host loop below.
+            from perceiver_amd.ops import sample as _sample
+
+            vocab = self.backend_model.config.vocab_size
+            select_kernel = _sample.kernel_applicable(p.device, vocab)
+            # the graphed step embeds the fill token: ids outside the
+            # vocabulary stay on the host loop, which only writes them out
+            ids_ok = all(t is None or 0 <= t < vocab for t in (eos_token_id, pad_token_id))
+            if (p.device.type == "cuda" and ids_ok
+                    and (select_kernel or (eos_token_id is None and top_p is None
+                                           and generator is None))
                     and not bool((attention_mask == 0).any())
-                    and top_p is None and generator is None and max_new_tokens >= 3
+                    and max_new_tokens >= 3
                     and (seq_len - prefix_len) + max_new_tokens <= self.backend_model.max_latents
                     and seq_len + max_new_tokens <= self.backend_model.max_seq_len):
                 from perceiver_amd.core.graph_decode import GraphedDecoder
@@ -315,8 +330,9 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                 # storage: model.to(device/dtype) reallocates storage, and a
                 # captured graph replaying against the old pointers would
                 # silently use stale weights (in-place load_state_dict is fine)
-                key = (input_ids.shape[0], do_sample, float(temperature), top_k,
-                       bucket, p.device, p.dtype, p.data_ptr())
+                key = (input_ids.shape[0], bucket, p.device, p.dtype, p.data_ptr())
+                if not select_kernel:  # baked into the graph on the torch path
+                    key += (do_sample, float(temperature), top_k)
                 cache = getattr(self, "_graph_decoders", None)
                 if cache is None:
                     cache = self._graph_decoders = {}
@@ -330,10 +346,25 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                                           device=p.device, dtype=p.dtype,
                                           ca_capacity=bucket),
                         do_sample=do_sample, temperature=temperature, top_k=top_k)
-                gd.prefill(input_ids, prefix_len=prefix_len)
-                first = gd.tok.clone()  # token emitted by the prefill pass
-                rest = gd.decode(max_new_tokens - 1)
-                return torch.cat([input_ids, first, rest], dim=1)
+                if select_kernel:
+                    gd.set_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k,
+                                    top_p=top_p, eos_token_id=eos_token_id,
+                                    pad_token_id=pad_token_id)
+                first = gd.prefill(input_ids, prefix_len=prefix_len, generator=generator)
+                if eos_token_id is None:
+                    rest = gd.decode(max_new_tokens - 1)
+                    return torch.cat([input_ids, first, rest], dim=1)
+                # EOS: replay in chunks of 16 and look at the done mask between
+                # them (one sync per 16 tokens), then cut where the host loop
+                # would have stopped: after the first step at which every row
+                # is done
+                new, left = [first], max_new_tokens - 1
+                while left > 0 and not bool(gd.finished.all()):
+                    n = min(16, left)
+                    new.append(gd.decode(n))
+                    left -= n
+                new = self._cut_at_all_done(torch.cat(new, dim=1), eos_token_id)
+                return torch.cat([input_ids, new], dim=1)
 
             # preallocated in-place cache: no per-step concat/realloc (K9)
             past = allocate_kv_cache(self.backend_model, input_ids.shape[0],
@@ -516,6 +547,15 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                 break
 
         return input_ids
+
+    @staticmethod
+    def _cut_at_all_done(new_tokens: torch.Tensor, eos_token_id: int) -> torch.Tensor:
+        """(batch, n) generated tokens cut after the first column by which every
+        row has emitted EOS: the length at which the host loop breaks."""
+        all_done = (new_tokens == eos_token_id).int().cummax(dim=1).values.bool().all(dim=0)
+        if not bool(all_done.any()):
+            return new_tokens
+        return new_tokens[:, :int(all_done.int().argmax()) + 1]
 
     @staticmethod
     def _select_next(logits, do_sample, temperature, top_k, top_p, generator):

@@ -33,6 +33,15 @@ torch::Tensor transpose_bf16(torch::Tensor x);
 std::vector<torch::Tensor> gemm_wgrad(torch::Tensor dy, torch::Tensor x, bool want_db);
 bool gemm_wgrad_applicable(long M, long N, long K);
 std::tuple<int64_t, int64_t, int64_t, int64_t> wgrad_plan(int64_t M, int64_t N, int64_t K);
+torch::Tensor decode_select(torch::Tensor logits, torch::Tensor do_sample,
+                            torch::Tensor temperature, torch::Tensor top_k, torch::Tensor top_p,
+                            torch::Tensor seed, torch::Tensor draw,
+                            c10::optional<torch::Tensor> tok, c10::optional<torch::Tensor> out_buf,
+                            c10::optional<torch::Tensor> step, c10::optional<torch::Tensor> done,
+                            c10::optional<torch::Tensor> eos_fill);
+torch::Tensor decode_keep_mask(torch::Tensor logits, torch::Tensor temperature,
+                               torch::Tensor top_k, torch::Tensor top_p);
+bool decode_select_applicable(long V);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_fwd", &gelu_bias_fwd, "fused bias+GELU forward (bf16)");
@@ -69,4 +78,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     }, "shape gate for the weight-gradient GEMM");
     m.def("wgrad_plan", &wgrad_plan,
           "host-only: (tile_n, tile_k, nsplit, rows_per_split) of the weight-gradient GEMM");
+    m.def("decode_select", &decode_select,
+          "fused decode token selection (greedy / temperature, top-k, top-p) with EOS bookkeeping",
+          pybind11::arg("logits"), pybind11::arg("do_sample"), pybind11::arg("temperature"),
+          pybind11::arg("top_k"), pybind11::arg("top_p"), pybind11::arg("seed"),
+          pybind11::arg("draw"), pybind11::arg("tok") = pybind11::none(),
+          pybind11::arg("out_buf") = pybind11::none(), pybind11::arg("step") = pybind11::none(),
+          pybind11::arg("done") = pybind11::none(), pybind11::arg("eos_fill") = pybind11::none());
+    m.def("decode_keep_mask", &decode_keep_mask,
+          "debug entry of decode_select: the kept set of every row as a (B, V) bool mask");
+    m.def("decode_select_applicable", [](int64_t V) { return decode_select_applicable(V); },
+          "host-only: whether decode_select has a tier for a vocabulary of V");
 }
