@@ -183,6 +183,7 @@ inline SplitPlan plan_split(long blocks, long len, int tile) {
 struct FwdSplit {
     SplitPlan plan;
     long rows;  // B*H*Nq
+    long len;   // Lk, the split axis
     torch::Tensor o_part, lse_part;
     float* o_part_p = nullptr;
     float* lse_part_p = nullptr;
@@ -190,7 +191,7 @@ struct FwdSplit {
 
 inline FwdSplit make_fwd_split(const torch::Tensor& q, long Lk, long Dv, int qblk, int kvblk) {
     const long B = q.size(0), H = q.size(1), Nq = q.size(2);
-    FwdSplit s{plan_split((Nq + qblk - 1) / qblk * B * H, Lk, kvblk), B * H * Nq};
+    FwdSplit s{plan_split((Nq + qblk - 1) / qblk * B * H, Lk, kvblk), B * H * Nq, Lk};
     if (s.plan.nsplit > 1) {
         auto f32 = q.options().dtype(torch::kFloat32);
         s.o_part = torch::empty({(long)s.plan.nsplit, s.rows, Dv}, f32);

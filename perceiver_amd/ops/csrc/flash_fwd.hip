@@ -206,6 +206,10 @@ __global__ void flash_fwd_kernel(            // budget allows (not the 352 templ
                         if (padrow && j < Lk) masked |= padrow[j];
                         if (causal && j > Lk - Nq + qi) masked = true;
                         sv = masked ? -FLT_MAX : sv;
+                        // keys past Lk do not exist: -inf keeps them out of a
+                        // fully-masked row's uniform average (its l counts the
+                        // Lk real keys, as the reference's softmax does)
+                        if (j >= Lk) sv = -INFINITY;
                         s_acc[h][kb][r] = sv;
                         mx = fmaxf(mx, sv);
                     }
@@ -328,12 +332,18 @@ __global__ void flash_fwd_kernel(            // budget allows (not the 352 templ
 
 // Merge KV-split partials: one wave per (b,h,q) row.
 //   w_i = exp(lse_i - max) ; O = sum w_i O_i / sum w_i ; lse = max + log(sum w_i)
+// A row whose keys are masked in EVERY split (each partial lse is -FLT_MAX;
+// splits that visited no key at all carry -1e30) has no finite max to weight
+// by: each partial is then the uniform mean over its split's keys, so the
+// splits are weighted by their key counts and lse is -FLT_MAX, which is what
+// the unsplit kernels return for such a row.
 __global__ void flash_merge_kernel(const float* __restrict__ o_part,
                                    const float* __restrict__ lse_part,
                                    unsigned short* __restrict__ op,
                                    float* __restrict__ lsep,
                                    long osb, long osh, long osn, int H, int Nq,
-                                   long rows, int nsplit, int dv) {
+                                   long rows, int nsplit, int dv,
+                                   long kv_chunk, long Lk) {
     long row = (long)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
     int lane = threadIdx.x % 64;
     if (row >= rows) return;
@@ -343,9 +353,15 @@ __global__ void flash_merge_kernel(const float* __restrict__ o_part,
 
     float mx = -1e30f;
     for (int i = 0; i < nsplit; ++i) mx = fmaxf(mx, lse_part[(long)i * rows + row]);
+    const bool all_masked = mx <= -1e29f;
     float wsum = 0.f;
     for (int i = lane; i < nsplit; i += 64) {
-        float wv = __expf(lse_part[(long)i * rows + row] - mx);
+        float l = lse_part[(long)i * rows + row];
+        float wv = __expf(l - mx);
+        if (all_masked) {
+            long keys = min(Lk, (long)(i + 1) * kv_chunk) - (long)i * kv_chunk;
+            wv = (l < -0.5f * FLT_MAX) ? (float)keys : 0.f;
+        }
         wbuf[wv_id][i] = wv;
     }
     __builtin_amdgcn_s_waitcnt(0);
@@ -361,7 +377,7 @@ __global__ void flash_merge_kernel(const float* __restrict__ o_part,
             acc += wbuf[wv_id][i] * o_part[((long)i * rows + row) * dv + c];
         orow[c] = f2bf(acc * inv);
     }
-    if (lane == 0) lsep[row] = mx + logf(fmaxf(wsum, 1e-37f));
+    if (lane == 0) lsep[row] = all_masked ? -FLT_MAX : mx + logf(fmaxf(wsum, 1e-37f));
 }
 
 // fold the KV-split partials into out/lse (nothing to do without a split)
@@ -375,7 +391,8 @@ void merge_fwd_split(const FwdSplit& sp, torch::Tensor& out, torch::Tensor& lse,
                        reinterpret_cast<unsigned short*>(out.data_ptr()),
                        lse.data_ptr<float>(),
                        out.stride(0), out.stride(1), out.stride(2),
-                       (int)out.size(1), (int)out.size(2), sp.rows, sp.plan.nsplit, Dv);
+                       (int)out.size(1), (int)out.size(2), sp.rows, sp.plan.nsplit, Dv,
+                       sp.plan.chunk, sp.len);
     HIP_CHECK_LAST();
 }
 

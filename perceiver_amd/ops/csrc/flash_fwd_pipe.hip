@@ -50,7 +50,7 @@ template <int KGR, int VGR, int DMAX, int DVMAX>
 struct Staged {
     short8v k[KGR];
     short8v v[VGR];
-    float bias;     // lane < KVBLK: -FLT_MAX where key padded/oob, else 0
+    float bias;     // lane < KVBLK: -FLT_MAX where key padded, -inf where oob, else 0
 };
 
 template <int KGR, int VGR, int DMAX, int DVMAX>
@@ -79,9 +79,10 @@ DEVINL void stage_issue(Staged<KGR, VGR, DMAX, DVMAX>& st,
     }
     if (tid < KVBLK) {
         int j = kv0 + tid;
-        bool masked = j >= Lk;
-        if (padrow != nullptr && j < Lk) masked |= padrow[j];
-        st.bias = masked ? -FLT_MAX : 0.f;
+        bool masked = padrow != nullptr && j < Lk && padrow[j];
+        // keys past Lk do not exist: -inf (not the pad fill) keeps them out
+        // of a fully-masked row's uniform average over the Lk real keys
+        st.bias = j >= Lk ? -INFINITY : (masked ? -FLT_MAX : 0.f);
     }
 }
 
@@ -413,22 +414,22 @@ __global__ void flash_fwd_pipe_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     if (gridDim.z > 1) {
-        // split path: fp32 partials, scalar stores (rare: tiny grids only)
-        const char* orow_lds = o_mine;
+        // split path: fp32 partials, scalar stores (rare: tiny grids only).
+        // Taken from the accumulators, not the bf16 image staged above: the
+        // merge rounds to bf16 once, like the unsplit path
 #pragma unroll
         for (int h = 0; h < QH; ++h)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 int qi = q0 + h * 16 + hi4 * 4 + r;
                 if (qi >= Nq) continue;
+                float l_eff = l_run[h][r] * keep;
+                float inv_l = (l_eff > 0.f) ? 1.0f / l_eff : 0.f;
                 long row = ((long)blockIdx.z * B * H + bh) * Nq + qi;
                 float* od = o_part + row * DVMAX;  // Dv == DVMAX enforced by launcher
 #pragma unroll
-                for (int cb = 0; cb < CBLOCKS; ++cb) {
-                    int c = cb * 16 + lo16;
-                    od[c] = bf2f(*reinterpret_cast<const unsigned short*>(
-                        orow_lds + (h * 16 + hi4 * 4 + r) * OROW + c * 2));
-                }
+                for (int cb = 0; cb < CBLOCKS; ++cb)
+                    od[cb * 16 + lo16] = o_acc[h][cb][r] * inv_l;
             }
     } else {
         constexpr int GPR_O = DVMAX / 8;      // 16-B granules per row
