@@ -31,6 +31,14 @@ Design (vs. the host-driven path in ``PerceiverAR.forward``):
   tensor that a single ``add_`` advances after the kernel, so no block of the
   kernel races another on a counter. A decode of N tokens is N graph replays
   with zero host synchronisation.
+- Beam search (``num_beams > 1``): the caches hold ``bsz * num_beams`` rows and
+  the step ends with two launches instead of one, ``beam_select`` (per-group
+  top-k of score + log-softmax, done / gen_len / token / parent bookkeeping)
+  and ``beam_reorder`` (in-place permutation of the rows generated since the
+  prefill in every KV buffer, through one device-resident descriptor table).
+  The prompt rows of a group's beams are bit-identical copies of one prefill,
+  so only the generated rows ever move. Each step records (token, parent);
+  the histories are backtracked once, after the replays (``ops/beam.py``).
 
 The un-captured step (``_step``) runs eagerly on any device, which is what the
 CPU numerics test compares against the host-driven cached forward. The reference
@@ -43,6 +51,7 @@ from typing import List, Optional
 
 import torch
 
+from perceiver_amd.ops import beam as _beam
 from perceiver_amd.ops import sample as _sample
 
 _KEEP = object()  # set_sampling: leave this parameter as it is
@@ -66,8 +75,13 @@ class GraphedDecoder:
     def __init__(self, model, caches: List[StaticKVCache], use_graph: bool = True,
                  do_sample: bool = False, temperature: float = 1.0,
                  top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None):
-        """``do_sample``: in-graph ancestral sampling (temperature scaling,
+                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
+                 num_beams: int = 1):
+        """``num_beams > 1``: beam search. The caches' batch is ``bsz * num_beams``
+        (beams of one prompt are consecutive rows), ``prefill`` takes the ``bsz``
+        prompts, the sampling parameters are unused and ``best`` returns the
+        winning hypotheses.
+        ``do_sample``: in-graph ancestral sampling (temperature scaling,
         optional top-k and top-p truncation). On the GPU the selection is the
         ``decode_select`` kernel with a counter-hash draw keyed by a per-prefill
         seed and a device draw index, so replays draw fresh randomness with zero
@@ -117,10 +131,98 @@ class GraphedDecoder:
         self._generator = None
         self._steps_host = 0
         self._graph = None
+        self.num_beams = int(num_beams)
+        if self.num_beams > 1:
+            self._init_beams()
         self.do_sample, self.temperature, self.top_k, self.top_p = False, 1.0, None, None
         self.eos_token_id = self.pad_token_id = None
         self.set_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k,
                           top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id)
+
+    # -------------------------------------------------------------------- beams
+
+    def _init_beams(self):
+        nb, B, dev = self.num_beams, self.batch, self.device
+        if not _beam.in_range(self.vocab, nb):
+            raise ValueError(f"num_beams={nb} / vocabulary {self.vocab} outside the beam "
+                             f"decoder's range")
+        if B % nb:
+            raise ValueError(f"cache batch {B} is not a multiple of num_beams={nb}")
+        self.groups = B // nb
+        # decided once, like use_kernel: a captured graph holds whichever step it was built with
+        self.use_beam_kernel = _beam.kernel_applicable(dev, self.vocab, nb)
+        self.beam_scores = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.gen_len = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.beam_src = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.group_done = torch.zeros(self.groups, dtype=torch.bool, device=dev)
+        # per-step record, row r = the r'th generated token (0: from the prefill logits)
+        rows = (self.sa_cap or self.ca_cap) + 1
+        self.rec_tok = torch.zeros(rows, B, dtype=torch.long, device=dev)
+        self.rec_parent = torch.zeros(rows, B, dtype=torch.int32, device=dev)
+        self.rec_all_done = torch.zeros(rows, self.groups, dtype=torch.bool, device=dev)
+        self._reorder_bufs = [b for c in self.caches for b in (c.k_buf, c.v_buf)]
+        # length counter of each buffer: counters[0] (CA) or counters[1] (SA)
+        self._reorder_counter = [0 if i == 0 else 1 for i, c in enumerate(self.caches)
+                                 for _ in range(2)]
+        self.reorder_table = None
+        if self.use_beam_kernel:
+            self.reorder_table = _beam.reorder_table(
+                self._reorder_bufs, [0] * len(self._reorder_bufs), self._reorder_counter).to(dev)
+
+    def _beam_select_into_tok(self, logits: torch.Tensor, rec_offset: int):
+        """One beam step from (batch, vocab) logits: scores, done, gen_len, tok,
+        src and the record row ``step_idx + rec_offset``. One launch on the GPU."""
+        nb = self.num_beams
+        if self.use_beam_kernel:
+            from perceiver_amd.ops import hip
+
+            hip.ext().beam_select(
+                logits, self.beam_scores, self.done, self.gen_len, self.tok.view(-1),
+                self.beam_src, self.group_done, self.eos_fill, nb, step=self.step_idx,
+                rec_offset=rec_offset, rec_tok=self.rec_tok, rec_parent=self.rec_parent,
+                rec_all_done=self.rec_all_done)
+            return
+        src, tok, score, done, gen_len, all_done = _beam.beam_select_reference(
+            logits, self.beam_scores, self.done, self.gen_len, nb, self.eos_fill[0],
+            self.eos_fill[1])
+        self.beam_src.copy_(src)
+        self.tok.copy_(tok[:, None])
+        self.beam_scores.copy_(score)
+        self.done.copy_(done)
+        self.gen_len.copy_(gen_len)
+        self.group_done.copy_(all_done)
+        cur = self.step_idx + rec_offset
+        self.rec_tok.index_copy_(0, cur, tok[None])
+        self.rec_parent.index_copy_(0, cur, src[None])
+        self.rec_all_done.index_copy_(0, cur, all_done[None])
+
+    def _beam_reorder(self):
+        if self.use_beam_kernel:
+            _beam.beam_reorder(self.reorder_table, self.counters, self.beam_src, self.num_beams)
+        else:
+            _beam.reorder_reference(self._reorder_bufs, self.beam_src, self.num_beams)
+
+    def hypotheses(self) -> torch.Tensor:
+        """(batch, 1 + steps) tokens of every current beam since the prefill."""
+        return _beam.backtrack(self.rec_tok, self.rec_parent, self.num_beams,
+                               self._steps_host + 1)
+
+    def best(self, length_penalty: float = 1.0):
+        """Per prompt the hypothesis with the largest
+        ``score / clamp(gen_len, 1) ** length_penalty``: ``(tokens, scores)`` of
+        shapes (bsz, 1 + steps) and (bsz,). The tokens are cut after the first
+        step at which every beam of every prompt was done, where the host loop
+        stops."""
+        nb = self.num_beams
+        norm = self.gen_len.view(-1, nb).float().clamp(min=1.0) ** length_penalty
+        scores = self.beam_scores.view(-1, nb)
+        pick = (scores / norm).argmax(dim=-1)
+        rows = pick + torch.arange(self.groups, device=self.device) * nb
+        toks = self.hypotheses().index_select(0, rows)
+        stop = self.rec_all_done[:self._steps_host + 1].all(dim=1)
+        if bool(stop.any()):
+            toks = toks[:, :int(stop.int().argmax()) + 1]
+        return toks, scores.gather(1, pick[:, None]).squeeze(1)
 
     # ----------------------------------------------------------------- sampling
 
@@ -159,7 +261,7 @@ class GraphedDecoder:
         self.eos_fill.copy_(torch.tensor([self._eos, self._fill], dtype=torch.long))
         ds = self.do_sample
         self._any_sample = bool(ds.any()) if isinstance(ds, torch.Tensor) else bool(ds)
-        if not self.use_kernel:
+        if not self.use_kernel and self.num_beams == 1:  # the beam step reads eos_fill itself
             self._graph = None
 
     @property
@@ -185,10 +287,12 @@ class GraphedDecoder:
             # store keys pre-rotated at their absolute positions: the decode
             # step then never touches cached rows again (no O(cache) re-rotate)
             c.pre_rotated = True
-        out = self.model(prompt, prefix_len=prefix_len, kv_cache=self.caches)
-
         n0 = prompt.shape[1]
         prefix0 = prefix_len
+        if self.num_beams > 1:
+            return self._prefill_beams(prompt, prefix_len)
+        out = self.model(prompt, prefix_len=prefix_len, kv_cache=self.caches)
+
         self.ca_len.fill_(n0)
         self.sa_len.fill_(n0 - prefix0)
         self.step_idx.fill_(0)
@@ -204,6 +308,53 @@ class GraphedDecoder:
             raise RuntimeError("a generator on the captured-graph path needs the decode_select "
                                "kernel (PERCEIVER_DECODE_SELECT=0 or an unsupported vocabulary)")
         self._select_into_tok(out.logits[:, -1, :], record=False)
+        self.draw_idx.fill_(1)
+
+        self.ca_len_host = n0
+        self.sa_len_host = n0 - prefix0
+        self._steps_host = 0
+        self.caches[0].enable_graph_append(self.ca_len)
+        for c in self.caches[1:]:
+            c.enable_graph_append(self.sa_len)
+        return self.tok.clone()
+
+    def _prefill_beams(self, prompt: torch.Tensor, prefix_len: int) -> torch.Tensor:
+        """Beam prefill: the ``bsz`` prompts run replicated, then beam 0's cache
+        rows and logits are broadcast over its group. A replicated batch through
+        library GEMMs is not guaranteed bit-identical row to row, and reordering
+        only the generated rows is exact only if the prompt rows are."""
+        nb, G = self.num_beams, self.groups
+        if prompt.shape[0] != G:
+            raise ValueError(f"beam prefill takes {G} prompts, got {prompt.shape[0]}")
+        n0, prefix0 = prompt.shape[1], prefix_len
+        out = self.model(prompt.repeat_interleave(nb, dim=0), prefix_len=prefix_len,
+                         kv_cache=self.caches)
+        for i, c in enumerate(self.caches):
+            n = n0 if i == 0 else n0 - prefix0
+            for buf in (c.k_buf, c.v_buf):
+                v = buf.view(G, nb, *buf.shape[1:])
+                v[:, 1:, :n].copy_(v[:, :1, :n].expand(-1, nb - 1, -1, -1))
+        logits = out.logits[:, -1, :]
+        logits = logits.view(G, nb, -1)[:, :1].expand(-1, nb, -1).reshape(G * nb, -1)
+        self.last_logits = logits[:, None, :]
+
+        self.ca_len.fill_(n0)
+        self.sa_len.fill_(n0 - prefix0)
+        self.step_idx.fill_(0)
+        self.draw_idx.fill_(0)
+        self.done.zero_()
+        self.gen_len.zero_()
+        self.group_done.zero_()
+        self.rec_all_done.zero_()
+        start = torch.full((G, nb), -1e9, dtype=torch.float32)
+        start[:, 0] = 0.0
+        self.beam_scores.copy_(start.view(-1))
+        if self.reorder_table is not None:
+            # the rows a request generates start where its prompt ends
+            row0 = torch.tensor([n0 if ci == 0 else n0 - prefix0
+                                 for ci in self._reorder_counter], dtype=torch.long)
+            self.reorder_table[:, 4].copy_(row0)
+        self._beam_select_into_tok(logits, rec_offset=0)
         self.draw_idx.fill_(1)
 
         self.ca_len_host = n0
@@ -297,7 +448,11 @@ class GraphedDecoder:
 
         # token selection + bookkeeping, all on-device: the graph is self-advancing
         self.last_logits = logits  # graph-pool tensor: valid until the next replay
-        self._select_into_tok(logits[:, -1, :], record=True)
+        if self.num_beams > 1:
+            self._beam_select_into_tok(logits[:, -1, :], rec_offset=1)
+            self._beam_reorder()
+        else:
+            self._select_into_tok(logits[:, -1, :], record=True)
         self.counters.add_(1)  # cache lengths, step cursor and draw index together
 
     def _capture(self):
@@ -314,8 +469,10 @@ class GraphedDecoder:
             self._step()
 
     @torch.no_grad()
-    def decode(self, n: int) -> torch.Tensor:
-        """Generate the next ``n`` tokens after ``prefill``; returns (batch, n).
+    def decode(self, n: int, tokens: bool = True) -> Optional[torch.Tensor]:
+        """Generate the next ``n`` tokens after ``prefill``; returns (batch, n),
+        or None with ``tokens=False`` (a beam caller that only wants ``best``
+        spares the backtrack).
         May be called repeatedly after one prefill (``generate`` decodes in
         chunks to look at ``finished`` in between). The first call captures the
         step graph (2 warmup steps run eagerly and count toward ``n``); later
@@ -343,5 +500,10 @@ class GraphedDecoder:
         # self.tok this yields the n generated tokens after the prefill token.
         s0 = self._steps_host
         self._steps_host += n
+        if not tokens:
+            return None
+        if self.num_beams > 1:
+            # the current beams' last n tokens; a later step may still permute them
+            return self.hypotheses()[:, s0 + 1:]
         first = self.out_buf[:, s0 + 1:s0 + n]
         return torch.cat([first, self.tok], dim=1)

@@ -272,6 +272,12 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if num_beams > 1:
+            if use_cache and static_cache:
+                out = self._beam_search_graphed(input_ids, attention_mask, prefix_len, num_beams,
+                                                max_new_tokens, eos_token_id, pad_token_id,
+                                                length_penalty)
+                if out is not None:
+                    return out
             return self._beam_search(input_ids, attention_mask, prefix_len, num_beams,
                                      max_new_tokens, eos_token_id, pad_token_id,
                                      length_penalty, use_cache, static_cache)
@@ -394,6 +400,67 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                 break
 
         return input_ids
+
+    @torch.no_grad()
+    def _beam_search_graphed(self, input_ids, attention_mask, prefix_len, num_beams,
+                             max_new_tokens, eos_token_id, pad_token_id, length_penalty):
+        """Beam search on the captured decode graph, under the gating greedy has
+        (GPU, kernels applicable, no padding, ids inside the vocabulary, at least
+        3 new tokens, the request inside the latent-growth phase) plus
+        ``2 <= num_beams <= 8``. Returns None when the request is outside the
+        gate: the host loop ``_beam_search`` runs then.
+
+        One decoder (captured graph + caches of ``bsz * num_beams`` rows) is kept
+        per (bsz, num_beams, bucket); EOS and fill ids live in device memory, so
+        requests that differ in them or in prompt length replay the same graph."""
+        from perceiver_amd.ops import beam as _beam
+
+        bm = self.backend_model
+        p = next(bm.parameters())
+        vocab = bm.config.vocab_size
+        bsz, seq_len = input_ids.shape
+        ids_ok = all(t is None or 0 <= t < vocab for t in (eos_token_id, pad_token_id))
+        if not (p.device.type == "cuda" and ids_ok
+                and _beam.kernel_applicable(p.device, vocab, num_beams)
+                and not bool((attention_mask == 0).any())
+                and max_new_tokens >= 3
+                and (seq_len - prefix_len) + max_new_tokens <= bm.max_latents
+                and seq_len + max_new_tokens <= bm.max_seq_len):
+            return None
+        from perceiver_amd.core.graph_decode import GraphedDecoder
+
+        need = seq_len + max_new_tokens
+        bucket = 2048
+        while bucket < need:
+            bucket *= 2
+        bucket = min(bucket, bm.max_seq_len)
+        key = (bsz * num_beams, bucket, p.device, p.dtype, p.data_ptr(), num_beams)
+        cache = getattr(self, "_graph_decoders", None)
+        if cache is None:
+            cache = self._graph_decoders = {}
+        gd = cache.get(key)
+        if gd is None:
+            if len(cache) >= 2:  # bound held cache memory
+                cache.pop(next(iter(cache)))
+            gd = cache[key] = GraphedDecoder(
+                bm, allocate_kv_cache(bm, bsz * num_beams, device=p.device, dtype=p.dtype,
+                                      ca_capacity=bucket),
+                num_beams=num_beams)
+        # the host loop's fill: the pad id, else EOS, else 0
+        gd.set_sampling(eos_token_id=eos_token_id, pad_token_id=pad_token_id)
+        gd.prefill(input_ids, prefix_len=prefix_len)
+        left = max_new_tokens - 1
+        if eos_token_id is None:
+            gd.decode(left, tokens=False)
+        else:
+            # chunks of 16 with one look at the done mask in between; best() cuts
+            # the output where the host loop would have stopped
+            while left > 0 and not bool(gd.finished.all()):
+                n = min(16, left)
+                gd.decode(n, tokens=False)
+                left -= n
+        tokens, _ = gd.best(length_penalty)
+        return torch.cat([input_ids, tokens], dim=1)
 
     @torch.no_grad()
     def _beam_search(self, input_ids, attention_mask, prefix_len, num_beams,

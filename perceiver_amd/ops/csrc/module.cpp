@@ -42,6 +42,15 @@ torch::Tensor decode_select(torch::Tensor logits, torch::Tensor do_sample,
 torch::Tensor decode_keep_mask(torch::Tensor logits, torch::Tensor temperature,
                                torch::Tensor top_k, torch::Tensor top_p);
 bool decode_select_applicable(long V);
+void beam_select(torch::Tensor logits, torch::Tensor score, torch::Tensor done,
+                 torch::Tensor gen_len, torch::Tensor tok, torch::Tensor src,
+                 torch::Tensor all_done, torch::Tensor eos_fill, int64_t num_beams,
+                 c10::optional<torch::Tensor> step, int64_t rec_offset,
+                 c10::optional<torch::Tensor> rec_tok, c10::optional<torch::Tensor> rec_parent,
+                 c10::optional<torch::Tensor> rec_all_done);
+bool beam_select_applicable(long V, long num_beams);
+void beam_reorder(torch::Tensor table, torch::Tensor counters, torch::Tensor src,
+                  int64_t num_beams);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_fwd", &gelu_bias_fwd, "fused bias+GELU forward (bf16)");
@@ -89,4 +98,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "debug entry of decode_select: the kept set of every row as a (B, V) bool mask");
     m.def("decode_select_applicable", [](int64_t V) { return decode_select_applicable(V); },
           "host-only: whether decode_select has a tier for a vocabulary of V");
+    m.def("beam_select", &beam_select,
+          "one beam-search step per group of num_beams rows: top-k of score + log-softmax with "
+          "done / gen_len / token / parent bookkeeping",
+          pybind11::arg("logits"), pybind11::arg("score"), pybind11::arg("done"),
+          pybind11::arg("gen_len"), pybind11::arg("tok"), pybind11::arg("src"),
+          pybind11::arg("all_done"), pybind11::arg("eos_fill"), pybind11::arg("num_beams"),
+          pybind11::arg("step") = pybind11::none(), pybind11::arg("rec_offset") = 0,
+          pybind11::arg("rec_tok") = pybind11::none(),
+          pybind11::arg("rec_parent") = pybind11::none(),
+          pybind11::arg("rec_all_done") = pybind11::none());
+    m.def("beam_select_applicable",
+          [](int64_t V, int64_t num_beams) { return beam_select_applicable(V, num_beams); },
+          "host-only: whether beam_select takes a vocabulary of V with num_beams beams");
+    m.def("beam_reorder", &beam_reorder,
+          "in-place permutation of the generated rows of every described cache buffer by the "
+          "per-group source beams",
+          pybind11::arg("table"), pybind11::arg("counters"), pybind11::arg("src"),
+          pybind11::arg("num_beams"));
 }
