@@ -25,7 +25,8 @@ import torch.nn as nn
 
 from perceiver_amd.core.position import RotaryPositionEmbedding
 from perceiver_amd.ops.linear import PerceiverLinear
-from perceiver_amd.core.utils import ModuleOutput, Residual, init_parameters
+from perceiver_amd.core.utils import (ModuleOutput, Residual, fused_residual_enabled,
+                                       init_parameters, materialize)
 from perceiver_amd.core.adapter import (
     InputAdapter,
     OutputAdapter,
@@ -145,6 +146,18 @@ class MultiHeadAttention(nn.Module):
         if hasattr(self, "qkv_proj"):
             if x_q is x_kv:
                 qkv = self.qkv_proj(x_q)
+                if rot_pos_emb_q is None and rot_pos_emb_k is None and kv_cache is None:
+                    from perceiver_amd.ops.flash import can_pack_qkv_grad, packed_qkv_attention
+
+                    if can_pack_qkv_grad(qkv, self.num_heads, qk, vc, pad_mask,
+                                         self.attention_dropout, self.training):
+                        # same forward; the backward writes dq/dk/dv straight into
+                        # one d_qkv buffer instead of concatenating them
+                        o = packed_qkv_attention(
+                            qkv, self.num_heads, qk, vc, self.dp_scale, pad_mask,
+                            self.causal_attention, self.attention_dropout, self.training)
+                        o = self.o_proj(self._merge_heads(o))
+                        return ModuleOutput(last_hidden_state=o, kv_cache=kv_cache)
                 q, k, v = qkv.split([qk, qk, vc], dim=-1)
             else:
                 # same tensors, different inputs (e.g. cached decode through a
@@ -246,7 +259,27 @@ class CrossAttention(nn.Module):
         rot_pos_emb_k: Optional[RotaryPositionEmbedding] = None,
         kv_cache: Optional[KVCache] = None,
     ) -> ModuleOutput:
-        x_q = self.q_norm(x_q)
+        return self.forward_prenormed(
+            self.q_norm(x_q), x_kv=x_kv, x_kv_prefix=x_kv_prefix, pad_mask=pad_mask,
+            rot_pos_emb_q=rot_pos_emb_q, rot_pos_emb_k=rot_pos_emb_k, kv_cache=kv_cache,
+        )
+
+    @property
+    def residual_norm(self) -> LayerNorm:
+        """The LayerNorm a pending residual pair is summed in (see ``Residual``)."""
+        return self.q_norm
+
+    def forward_prenormed(
+        self,
+        x_q: torch.Tensor,
+        x_kv: Optional[torch.Tensor] = None,
+        x_kv_prefix: Optional[torch.Tensor] = None,
+        pad_mask: Optional[torch.Tensor] = None,
+        rot_pos_emb_q: Optional[RotaryPositionEmbedding] = None,
+        rot_pos_emb_k: Optional[RotaryPositionEmbedding] = None,
+        kv_cache: Optional[KVCache] = None,
+    ) -> ModuleOutput:
+        """``forward`` for an ``x_q`` that ``q_norm`` has already normalised."""
         if x_kv is None:
             x_kv = torch.cat([self.kv_norm(x_kv_prefix), x_q], dim=1)
         else:
@@ -296,7 +329,23 @@ class SelfAttention(nn.Module):
         rot_pos_emb: Optional[RotaryPositionEmbedding] = None,
         kv_cache: Optional[KVCache] = None,
     ) -> ModuleOutput:
-        x = self.norm(x)
+        return self.forward_prenormed(
+            self.norm(x), pad_mask=pad_mask, rot_pos_emb=rot_pos_emb, kv_cache=kv_cache
+        )
+
+    @property
+    def residual_norm(self) -> LayerNorm:
+        """The LayerNorm a pending residual pair is summed in (see ``Residual``)."""
+        return self.norm
+
+    def forward_prenormed(
+        self,
+        x: torch.Tensor,
+        pad_mask: Optional[torch.Tensor] = None,
+        rot_pos_emb: Optional[RotaryPositionEmbedding] = None,
+        kv_cache: Optional[KVCache] = None,
+    ) -> ModuleOutput:
+        """``forward`` for an ``x`` that ``norm`` has already normalised."""
         return self.attention(
             x, x, pad_mask=pad_mask, rot_pos_emb_q=rot_pos_emb,
             rot_pos_emb_k=rot_pos_emb, kv_cache=kv_cache,
@@ -311,9 +360,18 @@ class AbstractAttentionLayer(nn.Sequential):
         v_cache = torch.empty(x.shape[0], 0, self.num_v_channels, dtype=x.dtype, device=x.device)
         return k_cache, v_cache
 
-    def forward(self, *args, kv_cache: Optional[KVCache] = None, **kwargs) -> ModuleOutput:
-        attn_output = self[0](*args, kv_cache=kv_cache, **kwargs)
-        mlp_output = self[1](attn_output.last_hidden_state)
+    def forward(self, *args, kv_cache: Optional[KVCache] = None, defer_residual: bool = False,
+                **kwargs) -> ModuleOutput:
+        """``args[0]`` may be the :class:`~perceiver_amd.core.utils.PendingResidual` of a preceding layer. The
+        attention block hands its own pair to the MLP block; with ``defer_residual``
+        the MLP block's pair is returned for the caller's next layer, otherwise the
+        layer ends the chain and returns the sum."""
+        if isinstance(self[0], Residual):
+            attn_output = self[0](*args, kv_cache=kv_cache, defer=kv_cache is None, **kwargs)
+        else:
+            args = (materialize(args[0]),) + args[1:]
+            attn_output = self[0](*args, kv_cache=kv_cache, **kwargs)
+        mlp_output = self[1](attn_output.last_hidden_state, defer=defer_residual)
         return ModuleOutput(last_hidden_state=mlp_output.last_hidden_state, kv_cache=attn_output.kv_cache)
 
 
@@ -390,6 +448,13 @@ class SelfAttentionLayer(AbstractAttentionLayer):
         )
 
 
+def takes_pending_residual(layer: nn.Module) -> bool:
+    """Whether ``layer`` accepts a :class:`~perceiver_amd.core.utils.PendingResidual` as input and the
+    ``defer_residual`` keyword: plain attention layers do, a layer wrapped for
+    activation checkpointing does not (its inputs must be tensors)."""
+    return isinstance(layer, AbstractAttentionLayer) and fused_residual_enabled()
+
+
 def activation_checkpoint_wrapper(layer: AbstractAttentionLayer, offload_to_cpu: bool = False):
     """Per-layer activation checkpointing via torch.utils.checkpoint (the reference
     uses fairscale's checkpoint_wrapper, modules.py:933-956; on MI355X with 288 GB
@@ -426,6 +491,9 @@ def activation_checkpoint_wrapper(layer: AbstractAttentionLayer, offload_to_cpu:
                 hidden = cp.checkpoint(run, *args, use_reentrant=False)
             return ModuleOutput(last_hidden_state=hidden, kv_cache=None)
 
+    for m in layer.modules():
+        if isinstance(m, Residual):
+            m.handover = False
     return _Checkpointed(layer)
 
 
@@ -482,20 +550,31 @@ class SelfAttentionBlock(nn.Sequential):
         rot_pos_emb: Optional[RotaryPositionEmbedding] = None,
         kv_cache: Optional[List[KVCache]] = None,
     ) -> ModuleOutput:
+        """``x`` may be the :class:`~perceiver_amd.core.utils.PendingResidual` of a preceding layer; the output
+        is always a tensor (the block ends the chain of its layers)."""
         if kv_cache is None:
             kv_cache_updated = None
         else:
+            x = materialize(x)
             if len(kv_cache) == 0:
                 kv_cache = [layer.empty_kv_cache(x) for layer in self]
             kv_cache_updated = []
 
+        last = len(self) - 1
         for i, layer in enumerate(self):
             use_rot = i < self.num_rotary_layers or self.num_rotary_layers == -1
+            kwargs = {}
+            if kv_cache is None and takes_pending_residual(layer):
+                # every layer but the last leaves its residual sum to the next one
+                kwargs["defer_residual"] = i < last
+            else:
+                x = materialize(x)
             out = layer(
                 x,
                 pad_mask=pad_mask,
                 rot_pos_emb=rot_pos_emb if use_rot else None,
                 kv_cache=None if kv_cache is None else kv_cache[i],
+                **kwargs,
             )
             x = out.last_hidden_state
             if kv_cache_updated is not None:
@@ -518,11 +597,19 @@ class MLP(nn.Sequential):
         )
 
     def forward(self, x: torch.Tensor) -> ModuleOutput:
+        return self.forward_prenormed(self[0](x))
+
+    @property
+    def residual_norm(self) -> LayerNorm:
+        """The LayerNorm a pending residual pair is summed in (see ``Residual``)."""
+        return self[0]
+
+    def forward_prenormed(self, h: torch.Tensor) -> ModuleOutput:
+        """``forward`` for an input that the leading LayerNorm has already normalised."""
         from perceiver_amd.ops.gelu import (GeluBias, LinearGeluBias, can_fuse_gelu_bias,
                                             can_fuse_linear_gelu)
 
-        if can_fuse_gelu_bias(x):
-            h = self[0](x)
+        if can_fuse_gelu_bias(h):
             if self[1].bias is not None and can_fuse_linear_gelu(h, self[1].weight):
                 # one kernel: GEMM + bias + GELU (epilogue-fused)
                 h = LinearGeluBias.apply(h, self[1].weight, self[1].bias)
@@ -531,7 +618,9 @@ class MLP(nn.Sequential):
                 h = GeluBias.apply(h.contiguous(), self[1].bias)
             h = self[3](h)
             return ModuleOutput(last_hidden_state=h)
-        return ModuleOutput(last_hidden_state=super().forward(x))
+        for layer in list(self)[1:]:
+            h = layer(h)
+        return ModuleOutput(last_hidden_state=h)
 
 
 class PerceiverEncoder(nn.Module):
@@ -631,7 +720,13 @@ class PerceiverEncoder(nn.Module):
         x_adapted = self.input_adapter(x)
         x_latent = self.latent_provider()
 
-        x_latent = self.cross_attn_1(x_latent, x_adapted, pad_mask=pad_mask).last_hidden_state
+        def cross_attend(layer, x_latent):
+            # the cross-attention layer leaves its residual sum to the first
+            # self-attention layer behind it
+            kwargs = {"defer_residual": True} if takes_pending_residual(layer) else {}
+            return layer(x_latent, x_adapted, pad_mask=pad_mask, **kwargs).last_hidden_state
+
+        x_latent = cross_attend(self.cross_attn_1, x_latent)
         x_latent = self.self_attn_1(x_latent).last_hidden_state
 
         cross_attn_n = self.cross_attn_n if self.extra_cross_attention_layer else self.cross_attn_1
@@ -639,7 +734,7 @@ class PerceiverEncoder(nn.Module):
 
         for i in range(1, self.num_self_attention_blocks):
             if i < self.num_cross_attention_layers:
-                x_latent = cross_attn_n(x_latent, x_adapted, pad_mask=pad_mask).last_hidden_state
+                x_latent = cross_attend(cross_attn_n, x_latent)
             x_latent = self_attn_n(x_latent).last_hidden_state
 
         if return_adapted_input:
@@ -835,6 +930,10 @@ class PerceiverAR(nn.Module):
             ca_kv_cache, *sa_kv_cache = kv_cache
             kv_cache_updated = []
 
+        ca_kwargs = {}
+        if kv_cache is None and takes_pending_residual(self.cross_attention):
+            # the first self-attention layer forms the cross-attention layer's sum
+            ca_kwargs["defer_residual"] = True
         ca_output = self.cross_attention(
             x_latent,
             x_kv_prefix=x_prefix,
@@ -842,6 +941,7 @@ class PerceiverAR(nn.Module):
             rot_pos_emb_q=RotaryPositionEmbedding(frq_pos_enc_q, right_align=True),
             rot_pos_emb_k=RotaryPositionEmbedding(frq_pos_enc_k, right_align=True),
             kv_cache=ca_kv_cache,
+            **ca_kwargs,
         )
         if kv_cache_updated is not None:
             kv_cache_updated.append(ca_output.kv_cache)

@@ -7,6 +7,7 @@ reference checkpoint format.
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 
 import torch
@@ -43,19 +44,93 @@ torch.utils._pytree.register_pytree_node(
 )
 
 
+class PendingResidual:
+    """The two halves of a residual block whose sum has not been formed: the branch
+    output ``hidden`` and the ``shortcut``. A residual block hands this pair to its
+    successor, whose first LayerNorm forms the sum and normalises it in one pass
+    (:func:`perceiver_amd.ops.norm.add_layer_norm`); wherever a chain of blocks ends
+    the pair is materialised with a plain add."""
+
+    __slots__ = ("hidden", "shortcut")
+
+    def __init__(self, hidden: torch.Tensor, shortcut: torch.Tensor):
+        self.hidden = hidden
+        self.shortcut = shortcut
+
+    def materialize(self) -> torch.Tensor:
+        return self.hidden + self.shortcut
+
+
+# A layer may return the pair: FSDP2 must find its two tensors like any others.
+torch.utils._pytree.register_pytree_node(
+    PendingResidual,
+    lambda p: ([p.hidden, p.shortcut], None),
+    lambda values, _: PendingResidual(*values),
+)
+
+
+def materialize(x):
+    """The tensor behind ``x``: the sum of a pending residual pair, or ``x`` itself."""
+    return x.materialize() if isinstance(x, PendingResidual) else x
+
+
+def fused_residual_enabled() -> bool:
+    """PERCEIVER_FUSED_RESIDUAL=0 restores the add-then-LayerNorm path everywhere."""
+    return os.environ.get("PERCEIVER_FUSED_RESIDUAL", "1") != "0"
+
+
 class Residual(nn.Module):
     """Residual connection around ``module`` with dropout on the module output.
 
     ``module`` must return a :class:`ModuleOutput`; the residual is added to its
     ``last_hidden_state`` and the (possibly present) ``kv_cache`` is passed through.
+
+    Residual-stream hand-over: a ``module`` that names its leading LayerNorm
+    (``residual_norm``) and can run on an already normalised input
+    (``forward_prenormed``) lets this block take a :class:`PendingResidual` as its
+    first argument, form the pending sum inside that LayerNorm, and keep the sum as
+    its own shortcut. With ``defer=True`` the block returns its own (hidden,
+    shortcut) pair instead of their sum, for a successor that does the same. Only
+    without residual dropout and without a kv cache; a ``defer`` that cannot be
+    honoured returns the sum as always.
     """
 
     def __init__(self, module: nn.Module, dropout: float = 0.0):
         super().__init__()
         self.module = module
         self.dropout = nn.Dropout(dropout)
+        # cleared by activation_checkpoint_wrapper: a checkpointed layer keeps the
+        # plain add-then-LayerNorm path
+        self.handover = True
 
-    def forward(self, *args, **kwargs):
+    def _hands_over(self, kwargs) -> bool:
+        return (
+            self.handover
+            and fused_residual_enabled()
+            and not (self.training and self.dropout.p > 0.0)
+            and kwargs.get("kv_cache") is None
+            and hasattr(self.module, "forward_prenormed")
+        )
+
+    def forward(self, *args, defer: bool = False, **kwargs):
+        if self._hands_over(kwargs):
+            from perceiver_amd.ops.norm import add_layer_norm
+
+            x = args[0]
+            pending = isinstance(x, PendingResidual)
+            shortcut, normed = add_layer_norm(
+                self.module.residual_norm,
+                x.hidden if pending else None,
+                x.shortcut if pending else x,
+            )
+            output = self.module.forward_prenormed(normed, *args[1:], **kwargs)
+            hidden = output.last_hidden_state
+            output.last_hidden_state = (
+                PendingResidual(hidden, shortcut) if defer else hidden + shortcut
+            )
+            return output
+
+        args = (materialize(args[0]),) + args[1:]
         output = self.module(*args, **kwargs)
         hidden = output.last_hidden_state
         shortcut = args[0]

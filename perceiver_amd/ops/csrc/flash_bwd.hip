@@ -676,10 +676,19 @@ void launch_flash_bwd(const torch::Tensor& dout, const torch::Tensor& q, const t
 
 }  // namespace
 
+bool flash_supported_impl(long d_qk, long d_v);
+
+// whether flash_bwd takes a packed qkv gradient buffer at these head dims:
+// every tier but the one that runs on zero-padded copies
+bool flash_bwd_packs_qkv_grad(long D, long Dv) {
+    return flash_supported_impl(D, Dv) && !pads_to_288(D, Dv);
+}
+
 std::vector<torch::Tensor> flash_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                                      torch::Tensor v, torch::Tensor out, torch::Tensor lse,
                                      c10::optional<torch::Tensor> pad_mask, bool causal,
-                                     double dropout_p, int64_t seed) {
+                                     double dropout_p, int64_t seed,
+                                     c10::optional<torch::Tensor> qkv_grad) {
     TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
     // last-dim contiguity suffices; the merged-heads (B,N,H,Dv) layouts the
     // forward now produces (and the matching grads) pass through zero-copy
@@ -695,13 +704,15 @@ std::vector<torch::Tensor> flash_bwd(torch::Tensor dout, torch::Tensor q, torch:
     // channels are exact — padded dout/out columns contribute 0 to delta, and
     // the padded dq/dk/dv columns are sliced off
     if (pads_to_288(D, Dv)) {
+        TORCH_CHECK(!has_tensor(qkv_grad),
+                    "flash_bwd: no packed qkv gradient on the head dims padded to 288");
         namespace F = torch::nn::functional;
         auto res = flash_bwd(F::pad(dout, F::PadFuncOptions({0, 288 - Dv})),
                              F::pad(q, F::PadFuncOptions({0, 288 - D})),
                              F::pad(k, F::PadFuncOptions({0, 288 - D})),
                              F::pad(v, F::PadFuncOptions({0, 288 - Dv})),
                              F::pad(out, F::PadFuncOptions({0, 288 - Dv})),
-                             lse, pad_mask, causal, dropout_p, seed);
+                             lse, pad_mask, causal, dropout_p, seed, c10::nullopt);
         return {res[0].narrow(-1, 0, D), res[1].narrow(-1, 0, D), res[2].narrow(-1, 0, Dv)};
     }
 
@@ -724,9 +735,31 @@ std::vector<torch::Tensor> flash_bwd(torch::Tensor dout, torch::Tensor q, torch:
     // grads live in merged-heads memory like the forward's out: the module's
     // head-merge transpose+reshape on each grad becomes a free view instead
     // of a 40 MB copy per tensor
-    auto dq = empty_merged_heads(q, q.size(3));
-    auto dk = empty_merged_heads(k, k.size(3));
-    auto dv = empty_merged_heads(v, v.size(3));
+    torch::Tensor dq, dk, dv;
+    if (has_tensor(qkv_grad)) {
+        // self-attention: the three grads are the column slices [dq | dk | dv]
+        // of one (B, N, 2*H*D + H*Dv) buffer, each still merged-heads memory
+        // with the buffer's row pitch, so the split's backward has nothing to
+        // concatenate. The kernels take the strides as they come.
+        const auto& g = *qkv_grad;
+        const long qk = (long)H * D, vc = (long)H * Dv, N = Nq;
+        TORCH_CHECK(k.size(2) == N && k.size(1) == H && v.size(1) == H,
+                    "flash_bwd: a packed qkv gradient needs q, k, v of one length and head count");
+        TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kBFloat16 && g.is_contiguous() &&
+                        g.dim() == 3 && g.size(0) == B && g.size(1) == N &&
+                        g.size(2) == 2 * qk + vc,
+                    "flash_bwd: qkv_grad must be a contiguous bf16 (B, N, 2*qk + v) buffer");
+        auto heads = [&](long c0, long width, long d) {
+            return g.narrow(2, c0, width).view({B, N, H, d}).permute({0, 2, 1, 3});
+        };
+        dq = heads(0, qk, D);
+        dk = heads(qk, qk, D);
+        dv = heads(2 * qk, vc, Dv);
+    } else {
+        dq = empty_merged_heads(q, q.size(3));
+        dk = empty_merged_heads(k, k.size(3));
+        dv = empty_merged_heads(v, v.size(3));
+    }
 
     c10::optional<torch::Tensor> pm;
     if (pad_mask.has_value() && pad_mask->defined()) pm = pad_mask->contiguous();

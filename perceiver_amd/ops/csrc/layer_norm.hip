@@ -4,7 +4,10 @@
 // Register caching uses compile-time CHUNKS (static indexing — guide §5.4 rule 20);
 // the backward computes dx AND the dW/db per-block partials in one fused pass
 // (tiled partial slab + the colsum finalize kernel). The forward's granule
-// walk and the slab layout live in row_common.h.
+// walk and the slab layout live in row_common.h. The residual stream runs
+// through the same kernels: the forward can form s = h + x on the way in
+// (add_ln_fwd), the backward can add the shortcut's gradient on the way out
+// (ln_bwd with ds), each bit-equal to the torch add it replaces.
 #include <ATen/cuda/CUDAContext.h>
 #include "row_common.h"
 
@@ -13,10 +16,15 @@ namespace {
 constexpr int LN_WPB = 4;  // waves (rows in flight) per block
 
 // CHUNKS = ceil(C / 512); lane handles 8 contiguous elems per chunk.
-template <int CHUNKS>
+// ADD: the row is the residual sum s = bf16(h + x) (torch's single rounding),
+// written out once and normalised from the rounded value, so y/mean/rstd
+// equal ln_fwd(s) while the separate add pass and the re-read of s are gone.
+template <int CHUNKS, bool ADD>
 __global__ void ln_fwd_kernel(const unsigned short* __restrict__ x,
+                              const unsigned short* __restrict__ h,
                               const unsigned short* __restrict__ w,
                               const unsigned short* __restrict__ b,
+                              unsigned short* __restrict__ s,
                               unsigned short* __restrict__ y,
                               float* __restrict__ mean_out, float* __restrict__ rstd_out,
                               long rows, int C, float eps) {
@@ -29,12 +37,24 @@ __global__ void ln_fwd_kernel(const unsigned short* __restrict__ x,
     float vals[CHUNKS][8];
     float sum = 0.f, sumsq = 0.f;
 #pragma unroll
-    for (int i = 0; i < CHUNKS; ++i)
-        visit_granule({xrow}, granule_col(lane, i), C, [&](int e, float (&v)[1]) {
-            vals[i][e] = v[0];
-            sum += v[0];
-            sumsq += v[0] * v[0];
-        });
+    for (int i = 0; i < CHUNKS; ++i) {
+        if constexpr (ADD) {
+            int c0 = granule_col(lane, i);
+            visit_granule({h + row * C, xrow}, c0, C, [&](int e, float (&v)[2]) {
+                float sv = bf2f(f2bf(v[0] + v[1]));
+                vals[i][e] = sv;
+                sum += sv;
+                sumsq += sv * sv;
+            });
+            store_granule_bf16(s + row * C, c0, C, [&](int e) { return vals[i][e]; });
+        } else {
+            visit_granule({xrow}, granule_col(lane, i), C, [&](int e, float (&v)[1]) {
+                vals[i][e] = v[0];
+                sum += v[0];
+                sumsq += v[0] * v[0];
+            });
+        }
+    }
     sum = wave_sum(sum);
     sumsq = wave_sum(sumsq);
     float mean = sum / C;
@@ -45,16 +65,30 @@ __global__ void ln_fwd_kernel(const unsigned short* __restrict__ x,
         rstd_out[row] = rstd;
     }
 
+    // weight and bias both arrive as granules; the branch is wave-uniform
 #pragma unroll
     for (int i = 0; i < CHUNKS; ++i) {
         int c0 = granule_col(lane, i);
         float o[8];
-        visit_granule({w}, c0, C, [&](int e, float (&v)[1]) {
-            float bb = b ? bf2f(b[c0 + e]) : 0.f;
-            o[e] = (vals[i][e] - mean) * rstd * v[0] + bb;
-        });
+        if (b)
+            visit_granule({w, b}, c0, C, [&](int e, float (&v)[2]) {
+                o[e] = (vals[i][e] - mean) * rstd * v[0] + v[1];
+            });
+        else
+            visit_granule({w}, c0, C, [&](int e, float (&v)[1]) {
+                float bb = 0.f;
+                o[e] = (vals[i][e] - mean) * rstd * v[0] + bb;
+            });
         store_granule_bf16(yrow, c0, C, [&](int e) { return o[e]; });
     }
+}
+
+// dx (+ ds): the residual gradient joins after dx is rounded to bf16, the
+// order of the separate bf16 add this replaces.
+template <bool HAS_DS>
+DEVINL float add_ds(float dx, unsigned short ds) {
+    if constexpr (HAS_DS) return bf2f(f2bf(dx)) + bf2f(ds);
+    return dx;
 }
 
 // The two backward kernels below each write out their own granule walk and
@@ -62,12 +96,13 @@ __global__ void ln_fwd_kernel(const unsigned short* __restrict__ x,
 // every restructuring tried moved which a*b+c the compiler contracts into
 // FMAs, and with it dx by one bf16 ulp in a few elements per million
 // (docs/kernels.md). Keep the two row bodies in step by hand.
-template <int CHUNKS>
+template <int CHUNKS, bool HAS_DS>
 __global__ void ln_bwd_dx_kernel(const unsigned short* __restrict__ dy,
                                  const unsigned short* __restrict__ x,
                                  const unsigned short* __restrict__ w,
                                  const float* __restrict__ mean_in,
                                  const float* __restrict__ rstd_in,
+                                 const unsigned short* __restrict__ ds,
                                  unsigned short* __restrict__ dx,
                                  long rows, int C) {
     long row = (long)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
@@ -78,7 +113,10 @@ __global__ void ln_bwd_dx_kernel(const unsigned short* __restrict__ dy,
     unsigned short* dxrow = dx + row * C;
     float mean = mean_in[row], rstd = rstd_in[row];
 
+    const unsigned short* dsrow = HAS_DS ? ds + row * C : nullptr;
+
     float g[CHUNKS][8], xh[CHUNKS][8];
+    short8v dsv[CHUNKS];  // whole ds granules, fetched with dy/x (dead without ds)
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < CHUNKS; ++i) {
@@ -89,6 +127,7 @@ __global__ void ln_bwd_dx_kernel(const unsigned short* __restrict__ dy,
             short8v dyv = *reinterpret_cast<const short8v*>(dyrow + c0);
             short8v xv = *reinterpret_cast<const short8v*>(xrow + c0);
             short8v wv = *reinterpret_cast<const short8v*>(w + c0);
+            if constexpr (HAS_DS) dsv[i] = *reinterpret_cast<const short8v*>(dsrow + c0);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float gg = bf2f((unsigned short)dyv[e]) * bf2f((unsigned short)wv[e]);
@@ -122,13 +161,15 @@ __global__ void ln_bwd_dx_kernel(const unsigned short* __restrict__ dy,
             short8v o;
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                o[e] = (short)f2bf(rstd * (g[i][e] - s1 - xh[i][e] * s2));
+                o[e] = (short)f2bf(add_ds<HAS_DS>(rstd * (g[i][e] - s1 - xh[i][e] * s2),
+                                                  HAS_DS ? (unsigned short)dsv[i][e] : 0));
             *reinterpret_cast<short8v*>(dxrow + c0) = o;
         } else if (c0 < C) {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 if (c0 + e < C)
-                    dxrow[c0 + e] = f2bf(rstd * (g[i][e] - s1 - xh[i][e] * s2));
+                    dxrow[c0 + e] = f2bf(add_ds<HAS_DS>(rstd * (g[i][e] - s1 - xh[i][e] * s2),
+                                                        HAS_DS ? dsrow[c0 + e] : 0));
         }
     }
 }
@@ -139,13 +180,21 @@ __global__ void ln_bwd_dx_kernel(const unsigned short* __restrict__ dy,
 // dx-only kernel runs the identical traffic in ~21 us. One wave per row,
 // grid-stride row loop, per-lane fp32 dw/db accumulators, LDS combine,
 // tiled partial slab (slab_index: same layout + finalize as colsum).
-template <int CHUNKS>
-__launch_bounds__(256, CHUNKS >= 3 ? 2 : 4)  // wide rows need >128 VGPRs
+//
+// The reduction grid leaves only 2-3 waves on a SIMD, too few to cover the
+// load latency with one row per wave in flight. PIPE therefore keeps the NEXT
+// row's whole granules (and its mean/rstd) in flight, packed as loaded, while
+// the current row is reduced and stored: the loads are issued as soon as the
+// first pass has unpacked the current row. The row arithmetic inside the two
+// arms is untouched, only where a whole granule's bits come from moves.
+template <int CHUNKS, bool HAS_DS, bool PIPE>
+__launch_bounds__(256, (CHUNKS >= 3 || PIPE) ? 2 : 4)  // wide rows need >128 VGPRs
 __global__ void ln_bwd_fused_kernel(const unsigned short* __restrict__ dy,
                                     const unsigned short* __restrict__ x,
                                     const unsigned short* __restrict__ w,
                                     const float* __restrict__ mean_in,
                                     const float* __restrict__ rstd_in,
+                                    const unsigned short* __restrict__ ds,
                                     unsigned short* __restrict__ dx,
                                     float* __restrict__ partial,
                                     long rows, int C) {
@@ -160,13 +209,36 @@ __global__ void ln_bwd_fused_kernel(const unsigned short* __restrict__ dy,
 #pragma unroll
         for (int e = 0; e < 8; ++e) { dwacc[i][e] = 0.f; dbacc[i][e] = 0.f; }
 
+    // the row in flight (PIPE): whole granules only, the ragged one is read in place
+    short8v dyq[CHUNKS], xq[CHUNKS], dsq[CHUNKS];
+    float meanq = 0.f, rstdq = 0.f;
+    auto issue = [&](long row) {
+        meanq = mean_in[row];
+        rstdq = rstd_in[row];
+#pragma unroll
+        for (int i = 0; i < CHUNKS; ++i) {
+            int c0 = lane * 8 + i * 512;
+            if (c0 + 8 <= C) {
+                dyq[i] = *reinterpret_cast<const short8v*>(dy + row * C + c0);
+                xq[i] = *reinterpret_cast<const short8v*>(x + row * C + c0);
+                if constexpr (HAS_DS) dsq[i] = *reinterpret_cast<const short8v*>(ds + row * C + c0);
+            }
+        }
+    };
+    if constexpr (PIPE)
+        if (wave0 < rows) issue(wave0);
+
     for (long row = wave0; row < rows; row += wstride) {
         const unsigned short* dyrow = dy + row * C;
         const unsigned short* xrow = x + row * C;
+        const unsigned short* dsrow = HAS_DS ? ds + row * C : nullptr;
         unsigned short* dxrow = dx + row * C;
-        float mean = mean_in[row], rstd = rstd_in[row];
+        float mean, rstd;
+        if constexpr (PIPE) { mean = meanq; rstd = rstdq; }
+        else { mean = mean_in[row]; rstd = rstd_in[row]; }
 
         float g[CHUNKS][8], xh[CHUNKS][8];
+        short8v dsv[CHUNKS];  // this row's whole ds granules (dead without ds)
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < CHUNKS; ++i) {
@@ -174,8 +246,16 @@ __global__ void ln_bwd_fused_kernel(const unsigned short* __restrict__ dy,
 #pragma unroll
             for (int e = 0; e < 8; ++e) { g[i][e] = 0.f; xh[i][e] = 0.f; }
             if (c0 + 8 <= C) {
-                short8v dyv = *reinterpret_cast<const short8v*>(dyrow + c0);
-                short8v xv = *reinterpret_cast<const short8v*>(xrow + c0);
+                short8v dyv, xv;
+                if constexpr (PIPE) {
+                    dyv = dyq[i];
+                    xv = xq[i];
+                    if constexpr (HAS_DS) dsv[i] = dsq[i];
+                } else {
+                    dyv = *reinterpret_cast<const short8v*>(dyrow + c0);
+                    xv = *reinterpret_cast<const short8v*>(xrow + c0);
+                    if constexpr (HAS_DS) dsv[i] = *reinterpret_cast<const short8v*>(dsrow + c0);
+                }
                 short8v wv = *reinterpret_cast<const short8v*>(w + c0);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -206,6 +286,8 @@ __global__ void ln_bwd_fused_kernel(const unsigned short* __restrict__ dy,
                 }
             }
         }
+        if constexpr (PIPE)
+            if (row + wstride < rows) issue(row + wstride);
         s1 = wave_sum(s1) / C;
         s2 = wave_sum(s2) / C;
 #pragma unroll
@@ -215,40 +297,57 @@ __global__ void ln_bwd_fused_kernel(const unsigned short* __restrict__ dy,
                 short8v o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
-                    o[e] = (short)f2bf(rstd * (g[i][e] - s1 - xh[i][e] * s2));
+                    o[e] = (short)f2bf(add_ds<HAS_DS>(rstd * (g[i][e] - s1 - xh[i][e] * s2),
+                                                      HAS_DS ? (unsigned short)dsv[i][e] : 0));
                 *reinterpret_cast<short8v*>(dxrow + c0) = o;
             } else if (c0 < C) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     if (c0 + e < C)
-                        dxrow[c0 + e] = f2bf(rstd * (g[i][e] - s1 - xh[i][e] * s2));
+                        dxrow[c0 + e] = f2bf(add_ds<HAS_DS>(rstd * (g[i][e] - s1 - xh[i][e] * s2),
+                                                            HAS_DS ? dsrow[c0 + e] : 0));
             }
         }
     }
 
-    // combine the block's waves (all cover the same column range) and emit
-    // one tiled partial row (layout shared with the colsum finalize)
-    __shared__ float red[2][ROW_MAXC];
-    for (int i = threadIdx.x; i < ROW_MAXC; i += blockDim.x) {
-        red[0][i] = 0.f;
-        red[1][i] = 0.f;
-    }
-    __syncthreads();
+    // Combine the block's waves (all cover the same column range) and emit one
+    // tiled partial row (layout shared with the colsum finalize). Every wave
+    // parks its accumulators in a slot of its own with 16-B LDS stores and the
+    // block sums the slots in wave order, dw first and db after it through the
+    // same slots: a fixed summation order, and none of the 2*C LDS atomics per
+    // wave (eight lanes to a bank) that the combine used to cost.
+    __shared__ __attribute__((aligned(16))) float red[LN_WPB][CHUNKS * 512];
+    const int wv = threadIdx.x / 64;
+    auto combine = [&](const float(&acc)[CHUNKS][8], int k) {
 #pragma unroll
-    for (int i = 0; i < CHUNKS; ++i) {
-        int c0 = lane * 8 + i * 512;
+        for (int i = 0; i < CHUNKS; ++i) {
+            float* slot = &red[wv][lane * 8 + i * 512];
+            *reinterpret_cast<float4v*>(slot) = float4v{acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+            *reinterpret_cast<float4v*>(slot + 4) =
+                float4v{acc[i][4], acc[i][5], acc[i][6], acc[i][7]};
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {
+            float t = red[0][c];
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-            if (c0 + e < C) {
-                atomicAdd(&red[0][c0 + e], dwacc[i][e]);  // LDS only
-                atomicAdd(&red[1][c0 + e], dbacc[i][e]);
-            }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        partial[slab_index(c, blockIdx.x, gridDim.x)] = red[0][c];
-        partial[slab_index(C + c, blockIdx.x, gridDim.x)] = red[1][c];
-    }
+            for (int v = 1; v < LN_WPB; ++v) t += red[v][c];
+            partial[slab_index(k * C + c, blockIdx.x, gridDim.x)] = t;
+        }
+    };
+    combine(dwacc, 0);
+    __syncthreads();  // the slots are read out before db overwrites them
+    combine(dbacc, 1);
+}
+
+template <int CHUNKS, bool ADD>
+void launch_ln_fwd(const torch::Tensor& x, const torch::Tensor* h, const torch::Tensor& w,
+                   const c10::optional<torch::Tensor>& b, torch::Tensor* s, torch::Tensor& y,
+                   torch::Tensor& mean, torch::Tensor& rstd, long rows, int C, float eps) {
+    hipLaunchKernelGGL((ln_fwd_kernel<CHUNKS, ADD>), dim3((rows + LN_WPB - 1) / LN_WPB),
+                       dim3(64 * LN_WPB), 0, at::cuda::getCurrentCUDAStream(), bf16_ptr(x),
+                       ADD ? bf16_ptr(*h) : nullptr, bf16_ptr(w), opt_bf16_ptr(b),
+                       ADD ? bf16_ptr(*s) : nullptr, bf16_ptr(y), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), rows, C, eps);
 }
 
 }  // namespace
@@ -267,42 +366,88 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor w, c10::optiona
     if (rows == 0) return {y, mean, rstd};
     if (has_tensor(b)) b = b->contiguous();
     dispatch_chunks(C, [&](auto chunks) {
-        hipLaunchKernelGGL((ln_fwd_kernel<decltype(chunks)::value>),
-                           dim3((rows + LN_WPB - 1) / LN_WPB), dim3(64 * LN_WPB), 0,
-                           at::cuda::getCurrentCUDAStream(), bf16_ptr(x), bf16_ptr(wc),
-                           opt_bf16_ptr(b), bf16_ptr(y), mean.data_ptr<float>(),
-                           rstd.data_ptr<float>(), rows, C, (float)eps);
+        launch_ln_fwd<decltype(chunks)::value, false>(x, nullptr, wc, b, nullptr, y, mean, rstd,
+                                                      rows, C, (float)eps);
     });
     HIP_CHECK_LAST();
     return {y, mean, rstd};
 }
 
+// s = h + x (one bf16 rounding, as torch's add) and y = LayerNorm(s) in one
+// pass: returns {s, y, mean, rstd}, y/mean/rstd as ln_fwd(s) gives them.
+std::vector<torch::Tensor> add_ln_fwd(torch::Tensor h, torch::Tensor x, torch::Tensor w,
+                                      c10::optional<torch::Tensor> b, double eps) {
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(h.is_cuda() && h.scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(h.sizes() == x.sizes(), "add_ln_fwd: h and x must have one shape");
+    h = h.contiguous();
+    x = x.contiguous();
+    auto wc = w.contiguous();
+    int C = x.size(-1);
+    TORCH_CHECK(C <= ROW_MAXC, "add_ln_fwd: C must be <= 2048");
+    long rows = x.numel() / C;
+    auto s = torch::empty_like(x);
+    auto y = torch::empty_like(x);
+    auto mean = torch::empty({rows}, x.options().dtype(torch::kFloat32));
+    auto rstd = torch::empty_like(mean);
+    if (rows == 0) return {s, y, mean, rstd};
+    if (has_tensor(b)) b = b->contiguous();
+    dispatch_chunks(C, [&](auto chunks) {
+        launch_ln_fwd<decltype(chunks)::value, true>(x, &h, wc, b, &s, y, mean, rstd, rows, C,
+                                                     (float)eps);
+    });
+    HIP_CHECK_LAST();
+    return {s, y, mean, rstd};
+}
+
+// With ds (the gradient arriving on the residual shortcut, shaped like x) the
+// first result is bf16(dx) + ds, the sum autograd's fan-in add would form.
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w,
-                                  torch::Tensor mean, torch::Tensor rstd, bool needs_dwdb) {
+                                  torch::Tensor mean, torch::Tensor rstd, bool needs_dwdb,
+                                  c10::optional<torch::Tensor> ds) {
     dy = dy.contiguous(); x = x.contiguous();
     auto wc = w.contiguous();
     int C = x.size(-1);
     long rows = x.numel() / C;
+    const bool has_ds = has_tensor(ds);
+    if (has_ds) {
+        TORCH_CHECK(ds->scalar_type() == torch::kBFloat16 && ds->sizes() == x.sizes(),
+                    "ln_bwd: ds must be bf16 and shaped like x");
+        ds = ds->contiguous();
+    }
     auto dx = torch::empty_like(x);
     if (rows == 0) return {dx, torch::zeros_like(w), torch::zeros_like(w)};
     // dx only: one row per wave. Otherwise the fused single pass: dx +
     // per-block dw/db partials on the reduction grid + the shared finalize.
     const long nblocks = needs_dwdb ? reduction_blocks(rows, LN_WPB) : (rows + LN_WPB - 1) / LN_WPB;
+    // The next-row prefetch pays where its registers cost no wave that the grid
+    // would use (measured at 16384x1280, 32768x1024, 65536x768): always
+    // without ds; with ds only from three chunks up, where two waves per SIMD
+    // are all the reduction grid places anyway. PERCEIVER_LN_BWD_PIPE=0/1
+    // forces it off/on for A/B runs.
+    static const long pipe_env = env_int("PERCEIVER_LN_BWD_PIPE", -1);
+    const bool pipe = pipe_env < 0 ? (!has_ds || C > 1024) : pipe_env != 0;
     torch::Tensor partial;
     if (needs_dwdb) partial = empty_slab(x, 2 * (long)C, nblocks);
     dispatch_chunks(C, [&](auto chunks) {
         constexpr int CHUNKS = decltype(chunks)::value;
         auto stream = at::cuda::getCurrentCUDAStream();
-        if (needs_dwdb)
-            hipLaunchKernelGGL((ln_bwd_fused_kernel<CHUNKS>), dim3(nblocks), dim3(64 * LN_WPB), 0,
-                               stream, bf16_ptr(dy), bf16_ptr(x), bf16_ptr(wc),
-                               mean.data_ptr<float>(), rstd.data_ptr<float>(), bf16_ptr(dx),
-                               partial.data_ptr<float>(), rows, C);
-        else
-            hipLaunchKernelGGL((ln_bwd_dx_kernel<CHUNKS>), dim3(nblocks), dim3(64 * LN_WPB), 0,
-                               stream, bf16_ptr(dy), bf16_ptr(x), bf16_ptr(wc),
-                               mean.data_ptr<float>(), rstd.data_ptr<float>(), bf16_ptr(dx),
+        auto launch = [&](auto kernel, auto... tail) {
+            hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(64 * LN_WPB), 0, stream, bf16_ptr(dy),
+                               bf16_ptr(x), bf16_ptr(wc), mean.data_ptr<float>(),
+                               rstd.data_ptr<float>(), opt_bf16_ptr(ds), bf16_ptr(dx), tail...,
                                rows, C);
+        };
+        if (!needs_dwdb) {
+            if (has_ds) launch(ln_bwd_dx_kernel<CHUNKS, true>);
+            else launch(ln_bwd_dx_kernel<CHUNKS, false>);
+        } else {
+            float* part = partial.data_ptr<float>();
+            if (has_ds && pipe) launch(ln_bwd_fused_kernel<CHUNKS, true, true>, part);
+            else if (has_ds) launch(ln_bwd_fused_kernel<CHUNKS, true, false>, part);
+            else if (pipe) launch(ln_bwd_fused_kernel<CHUNKS, false, true>, part);
+            else launch(ln_bwd_fused_kernel<CHUNKS, false, false>, part);
+        }
     });
     HIP_CHECK_LAST();
     if (!needs_dwdb) return {dx, torch::Tensor(), torch::Tensor()};
@@ -310,3 +455,4 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tens
     colsum_reduce_partials(partial, acc, (int)nblocks, 2 * C);
     return {dx, acc[0], acc[1]};
 }
+

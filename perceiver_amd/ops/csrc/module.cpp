@@ -10,12 +10,17 @@ std::vector<torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k, torch::Te
 std::vector<torch::Tensor> flash_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                                      torch::Tensor v, torch::Tensor out, torch::Tensor lse,
                                      c10::optional<torch::Tensor> pad_mask, bool causal,
-                                     double dropout_p, int64_t seed);
+                                     double dropout_p, int64_t seed,
+                                     c10::optional<torch::Tensor> qkv_grad);
 std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b,
                                   double eps);
+std::vector<torch::Tensor> add_ln_fwd(torch::Tensor h, torch::Tensor x, torch::Tensor w,
+                                      c10::optional<torch::Tensor> b, double eps);
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w,
-                                  torch::Tensor mean, torch::Tensor rstd, bool needs_dwdb);
+                                  torch::Tensor mean, torch::Tensor rstd, bool needs_dwdb,
+                                  c10::optional<torch::Tensor> ds);
 bool flash_supported_impl(long d_qk, long d_v);
+bool flash_bwd_packs_qkv_grad(long D, long Dv);
 std::tuple<int64_t, int64_t> flash_split_plan(int64_t blocks, int64_t len, int64_t tile);
 bool flash_fwd_pipe_applicable(long D, long Dv, long Nq);
 void adamw_step(torch::Tensor master, torch::Tensor m, torch::Tensor v, torch::Tensor g,
@@ -56,18 +61,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_fwd", &gelu_bias_fwd, "fused bias+GELU forward (bf16)");
     m.def("gelu_bias_bwd", &gelu_bias_bwd, "fused bias+GELU backward (bf16)");
     m.def("flash_fwd", &flash_fwd, "fused flash attention forward");
-    m.def("flash_bwd", &flash_bwd, "fused flash attention backward");
+    m.def("flash_bwd", &flash_bwd,
+          "fused flash attention backward; with qkv_grad, a (B, N, 2*qk + v) bf16 buffer, dq/dk/dv "
+          "are written as its column slices and returned as views of it",
+          pybind11::arg("dout"), pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+          pybind11::arg("out"), pybind11::arg("lse"), pybind11::arg("pad_mask"),
+          pybind11::arg("causal"), pybind11::arg("dropout_p"), pybind11::arg("seed"),
+          pybind11::arg("qkv_grad") = pybind11::none());
     // needs_dropout is kept for callers; dropout runs in-kernel and never narrows the gate
     m.def("flash_supported", [](int64_t d_qk, int64_t d_v, int64_t /*needs_dropout*/) {
         return flash_supported_impl(d_qk, d_v);
     }, "shape gate for the flash kernel");
+    m.def("flash_bwd_packs_qkv_grad", [](int64_t d_qk, int64_t d_v) {
+        return flash_bwd_packs_qkv_grad(d_qk, d_v);
+    }, "host-only: whether flash_bwd accepts a packed qkv gradient buffer at these head dims");
     m.def("flash_split_plan", &flash_split_plan,
           "host-only: (nsplit, chunk) of the gridDim.z split for blocks workgroups over a len-long axis");
     m.def("flash_fwd_pipe_applicable", [](int64_t d, int64_t dv, int64_t nq) {
         return flash_fwd_pipe_applicable(d, dv, nq);
     }, "host-only: whether the pipelined forward has a template for (D, Dv) at Nq queries");
     m.def("ln_fwd", &ln_fwd, "fused bf16 LayerNorm forward");
-    m.def("ln_bwd", &ln_bwd, "fused bf16 LayerNorm backward");
+    m.def("add_ln_fwd", &add_ln_fwd,
+          "residual add + bf16 LayerNorm in one pass: returns (s = h + x, y, mean, rstd)");
+    m.def("ln_bwd", &ln_bwd,
+          "fused bf16 LayerNorm backward; with ds the first result is bf16(dx) + ds",
+          pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("mean"),
+          pybind11::arg("rstd"), pybind11::arg("needs_dwdb"),
+          pybind11::arg("ds") = pybind11::none());
     m.def("adamw_step", &adamw_step, "single-pass fused AdamW on flat fp32 state");
     m.def("rotary_apply", &rotary_apply, "fused rotary embedding (bf16, fwd/bwd via neg_sin)");
     m.def("dropout_add_fwd", &dropout_add_fwd, "fused residual dropout-add forward (bf16)");
