@@ -71,6 +71,7 @@ torch::Tensor transpose_bf16(torch::Tensor x) {
     x = x.contiguous();
     long N = x.size(0), K = x.size(1);
     auto out = torch::empty({K, N}, x.options());
+    if (x.numel() == 0) return out;  // a zero grid dimension is a launch error
     dim3 grid((N + TDIM - 1) / TDIM, (K + TDIM - 1) / TDIM);
     hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0,
                        at::cuda::getCurrentCUDAStream(), bf16_ptr(x), bf16_ptr(out), (int)N, (int)K);
