@@ -39,6 +39,16 @@ Design (vs. the host-driven path in ``PerceiverAR.forward``):
   The prompt rows of a group's beams are bit-identical copies of one prefill,
   so only the generated rows ever move. Each step records (token, parent);
   the histories are backtracked once, after the replays (``ops/beam.py``).
+- Left-padded prompt batches (``ragged=True``): ``prefill`` takes an
+  ``attention_mask`` whose rows are ``0…0 1…1`` and stores each row's pad count
+  in the device buffer ``shift``. The step then states the live keys of every
+  row as a ``KeyWindow`` of two device integers instead of a mask, keys
+  ``shift[b] .. ca_len`` for the cross-attention and ``0 .. sa_len`` for the
+  latent stack (which sees no pad mask on the host loop either), and the
+  query position is ``ca_len - shift[b]``. On the GPU the attention is the
+  ``decode_attn`` kernel (``ops/decode_attn.py``), which streams only those
+  keys; no mask tensor is built. The windows read ``counters`` and ``shift``,
+  so one captured graph serves every padding pattern of its batch size.
 
 The un-captured step (``_step``) runs eagerly on any device, which is what the
 CPU numerics test compares against the host-driven cached forward. The reference
@@ -53,6 +63,7 @@ import torch
 
 from perceiver_amd.ops import beam as _beam
 from perceiver_amd.ops import sample as _sample
+from perceiver_amd.ops.decode_attn import KeyWindow
 
 _KEEP = object()  # set_sampling: leave this parameter as it is
 
@@ -76,8 +87,10 @@ class GraphedDecoder:
                  do_sample: bool = False, temperature: float = 1.0,
                  top_k: Optional[int] = None, top_p: Optional[float] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
-                 num_beams: int = 1):
-        """``num_beams > 1``: beam search. The caches' batch is ``bsz * num_beams``
+                 num_beams: int = 1, ragged: bool = False):
+        """``ragged``: ``prefill`` accepts a left-padded ``attention_mask`` and the
+        step attends per-row key windows (module docstring). Not with beams.
+        ``num_beams > 1``: beam search. The caches' batch is ``bsz * num_beams``
         (beams of one prompt are consecutive rows), ``prefill`` takes the ``bsz``
         prompts, the sampling parameters are unused and ``best`` returns the
         winning hypotheses.
@@ -88,8 +101,12 @@ class GraphedDecoder:
         host round-trips; elsewhere it is the torch composition on torch's RNG.
         ``eos_token_id``: rows that emitted it keep emitting ``pad_token_id``
         (EOS itself when None) and are flagged in ``finished``."""
+        if ragged and int(num_beams) > 1:
+            raise ValueError("ragged=True with num_beams > 1: padded beam requests are not "
+                             "supported by the graphed decoder")
         self.model = model
         self.caches = caches
+        self.ragged = bool(ragged)
         p = next(model.parameters())
         self.device, self.dtype = p.device, p.dtype
         self.use_graph = use_graph and p.device.type == "cuda"
@@ -120,6 +137,8 @@ class GraphedDecoder:
         self.ar_sa = torch.arange(self.sa_cap, device=dev).unsqueeze(0)
         self.out_buf = torch.zeros(self.batch, self.sa_cap or self.ca_cap,
                                    dtype=torch.long, device=dev)
+        # ragged: pad count of every row, rewritten by each prefill
+        self.shift = torch.zeros(self.batch, dtype=torch.long, device=dev)
         # sampling parameters, per row, read by the kernel every step
         self.p_do_sample = torch.zeros(self.batch, dtype=torch.int32, device=dev)
         self.p_temperature = torch.ones(self.batch, dtype=torch.float32, device=dev)
@@ -273,9 +292,15 @@ class GraphedDecoder:
 
     @torch.no_grad()
     def prefill(self, prompt: torch.Tensor, prefix_len: int,
-                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                generator: Optional[torch.Generator] = None,
+                attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run the normal host-driven cached forward over the prompt, seed the
         device counters/buffers, and return the first selected token.
+
+        ``attention_mask`` (a ``ragged`` decoder only): (batch, n) with every row
+        ``0…0 1…1`` and at least one 1, anything else raises ``ValueError``. The
+        forward runs with ``pad_mask = ~attention_mask``, so positions are
+        shifted and clamped as ``PerceiverAR.forward`` does.
 
         Sampling draws a fresh seed here, from ``generator`` when given and
         otherwise from torch's global generator, and restarts the draw index:
@@ -289,9 +314,10 @@ class GraphedDecoder:
             c.pre_rotated = True
         n0 = prompt.shape[1]
         prefix0 = prefix_len
+        pad_mask = self._left_pad_mask(prompt, attention_mask)
         if self.num_beams > 1:
             return self._prefill_beams(prompt, prefix_len)
-        out = self.model(prompt, prefix_len=prefix_len, kv_cache=self.caches)
+        out = self.model(prompt, prefix_len=prefix_len, pad_mask=pad_mask, kv_cache=self.caches)
 
         self.ca_len.fill_(n0)
         self.sa_len.fill_(n0 - prefix0)
@@ -317,6 +343,27 @@ class GraphedDecoder:
         for c in self.caches[1:]:
             c.enable_graph_append(self.sa_len)
         return self.tok.clone()
+
+    def _left_pad_mask(self, prompt, attention_mask) -> Optional[torch.Tensor]:
+        """Validate ``attention_mask``, store the pad counts in ``shift`` and
+        return the forward's pad mask (None for a decoder that is not ragged)."""
+        if not self.ragged:
+            if attention_mask is not None and bool((attention_mask == 0).any()):
+                raise ValueError("a padded attention_mask needs GraphedDecoder(ragged=True)")
+            return None
+        if attention_mask is None:
+            self.shift.zero_()
+            return torch.zeros(prompt.shape, dtype=torch.bool, device=prompt.device)
+        live = attention_mask.to(prompt.device) != 0
+        if live.shape != prompt.shape:
+            raise ValueError(f"attention_mask has shape {tuple(live.shape)}, the prompt "
+                             f"{tuple(prompt.shape)}")
+        # 0…0 1…1: the last position is live and no live position precedes a pad
+        if not (bool(live[:, -1].all()) and bool((live[:, 1:] | ~live[:, :-1]).all())):
+            raise ValueError("attention_mask must be left-padded (every row 0…0 1…1 with at "
+                             "least one 1)")
+        self.shift.copy_((~live).sum(dim=1))
+        return ~live
 
     def _prefill_beams(self, prompt: torch.Tensor, prefix_len: int) -> torch.Tensor:
         """Beam prefill: the ``bsz`` prompts run replicated, then beam 0's cache
@@ -414,7 +461,10 @@ class GraphedDecoder:
         ``CausalSequenceModel.forward`` (modules.py) with full-capacity masked
         attention instead of host-length views."""
         m = self.model
-        pos_q = self.ca_len.view(1, 1).expand(self.batch, 1)
+        if self.ragged:
+            pos_q = (self.ca_len - self.shift).view(self.batch, 1)
+        else:
+            pos_q = self.ca_len.view(1, 1).expand(self.batch, 1)
         x, frq_q = m.input_adapter(self.tok, abs_pos=pos_q)
 
         # cross-attention: new token is the single latent; cached K/V at full
@@ -423,7 +473,10 @@ class GraphedDecoder:
         # position's row: q uses it directly, k uses it to rotate the new row
         # before it is appended.
         rot_now = RotaryPositionEmbedding(frq_q, right_align=True)
-        ca_mask = (self.ar_ca > self.ca_len).expand(self.batch, -1)
+        if self.ragged:  # two device integers per row, no mask tensor
+            ca_mask = KeyWindow(self.shift, self.ca_len)
+        else:
+            ca_mask = (self.ar_ca > self.ca_len).expand(self.batch, -1)
         ca_out = m.cross_attention(
             x,
             x_kv_prefix=x[:, :0],
@@ -433,7 +486,10 @@ class GraphedDecoder:
             kv_cache=self.caches[0],
         )
 
-        sa_mask = (self.ar_sa > self.sa_len).expand(self.batch, -1)
+        if self.ragged:
+            sa_mask = KeyWindow(None, self.sa_len)
+        else:
+            sa_mask = (self.ar_sa > self.sa_len).expand(self.batch, -1)
         sa_out = m.self_attention(
             ca_out.last_hidden_state,
             pad_mask=sa_mask,

@@ -312,14 +312,19 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
             # the graphed step embeds the fill token: ids outside the
             # vocabulary stay on the host loop, which only writes them out
             ids_ok = all(t is None or 0 <= t < vocab for t in (eos_token_id, pad_token_id))
+            # a left-padded batch decodes on a ragged decoder (per-row key
+            # windows, ops/decode_attn.py); any other padding keeps the host loop
+            padded = p.device.type == "cuda" and bool((attention_mask == 0).any())
             if (p.device.type == "cuda" and ids_ok
                     and (select_kernel or (eos_token_id is None and top_p is None
                                            and generator is None))
-                    and not bool((attention_mask == 0).any())
                     and max_new_tokens >= 3
                     and (seq_len - prefix_len) + max_new_tokens <= self.backend_model.max_latents
-                    and seq_len + max_new_tokens <= self.backend_model.max_seq_len):
+                    and seq_len + max_new_tokens <= self.backend_model.max_seq_len
+                    and (not padded or self._ragged_graph_ok(attention_mask, select_kernel))):
                 from perceiver_amd.core.graph_decode import GraphedDecoder
+
+                ragged = padded  # unpadded requests keep their decoder and cache key
 
                 # bucketed cache capacity: the graphed step reads the FULL
                 # (masked) CA cache every token, so size it to the request —
@@ -339,6 +344,8 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                 key = (input_ids.shape[0], bucket, p.device, p.dtype, p.data_ptr())
                 if not select_kernel:  # baked into the graph on the torch path
                     key += (do_sample, float(temperature), top_k)
+                if ragged:
+                    key += ("ragged",)
                 cache = getattr(self, "_graph_decoders", None)
                 if cache is None:
                     cache = self._graph_decoders = {}
@@ -351,12 +358,14 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                         allocate_kv_cache(self.backend_model, input_ids.shape[0],
                                           device=p.device, dtype=p.dtype,
                                           ca_capacity=bucket),
-                        do_sample=do_sample, temperature=temperature, top_k=top_k)
+                        do_sample=do_sample, temperature=temperature, top_k=top_k,
+                        ragged=ragged)
                 if select_kernel:
                     gd.set_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k,
                                     top_p=top_p, eos_token_id=eos_token_id,
                                     pad_token_id=pad_token_id)
-                first = gd.prefill(input_ids, prefix_len=prefix_len, generator=generator)
+                first = gd.prefill(input_ids, prefix_len=prefix_len, generator=generator,
+                                   attention_mask=attention_mask if ragged else None)
                 if eos_token_id is None:
                     rest = gd.decode(max_new_tokens - 1)
                     return torch.cat([input_ids, first, rest], dim=1)
@@ -400,6 +409,22 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                 break
 
         return input_ids
+
+    def _ragged_graph_ok(self, attention_mask, select_kernel: bool) -> bool:
+        """Whether a request whose mask holds zeros may take the graph path: every
+        row left-padded (``0…0 1…1`` with at least one 1), the select kernel
+        applies, and ``decode_attn`` takes every attention layer's head dims.
+        Right padding, holes and all-zero rows keep the host loop."""
+        from perceiver_amd.ops.decode_attn import decode_attn_applicable
+
+        if not select_kernel:
+            return False
+        for m in self.backend_model.modules():
+            if isinstance(m, MultiHeadAttention) and not decode_attn_applicable(
+                    m.num_qk_channels // m.num_heads, m.num_v_channels // m.num_heads):
+                return False
+        live = attention_mask != 0
+        return bool(live[:, -1].all()) and bool((live[:, 1:] | ~live[:, :-1]).all())
 
     @torch.no_grad()
     def _beam_search_graphed(self, input_ids, attention_mask, prefix_len, num_beams,

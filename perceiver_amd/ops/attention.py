@@ -12,12 +12,20 @@ Semantics (parity with /root/reference/perceiver/model/core/modules.py:90-170):
   - causal: mask = triu(Lk - Lq + 1), i.e. q/k right-aligned when lengths differ,
   - softmax over the key axis, optional dropout on the probabilities,
   - output = probs @ v.
+
+A ``KeyWindow(lo, hi)`` in the ``pad_mask`` slot (ops/decode_attn.py) states the
+live keys of every row as two device integers instead of a mask. At one query
+row, bf16 on the GPU, without dropout and with applicable head dims it runs the
+``decode_attn`` kernel; everything else builds the equivalent mask and takes the
+paths above.
 """
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
+
+from perceiver_amd.ops.decode_attn import KeyWindow
 
 
 def eager_attention(
@@ -76,6 +84,17 @@ def scaled_dot_attention(
 
     Batch-1 queries (learned latent/output-query arrays) broadcast against
     batch-N keys, matching the reference's einsum broadcasting."""
+    if isinstance(pad_mask, KeyWindow):
+        from perceiver_amd.ops import decode_attn as _da
+
+        # causal is right-aligned to the capacity: at one query row it masks
+        # nothing, so the kernel's window alone is the whole mask
+        if (q.shape[-2] == 1 and not (training and dropout_p > 0.0)
+                and _da.kernel_applicable(q, k, v)):
+            return _da.decode_attn(q, k, v, pad_mask.lo, pad_mask.hi)
+        return _da.window_attention_composition(
+            q, k, v, pad_mask.lo, pad_mask.hi, causal=causal, dropout_p=dropout_p,
+            training=training, max_heads_parallel=max_heads_parallel)
     if q.shape[0] != k.shape[0]:
         if q.shape[0] == 1:
             q = q.expand(k.shape[0], *q.shape[1:])

@@ -56,6 +56,10 @@ void beam_select(torch::Tensor logits, torch::Tensor score, torch::Tensor done,
 bool beam_select_applicable(long V, long num_beams);
 void beam_reorder(torch::Tensor table, torch::Tensor counters, torch::Tensor src,
                   int64_t num_beams);
+torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                          c10::optional<torch::Tensor> lo, torch::Tensor hi);
+bool decode_attn_applicable(long D, long Dv);
+std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t H, int64_t cap, int64_t D);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_fwd", &gelu_bias_fwd, "fused bias+GELU forward (bf16)");
@@ -118,6 +122,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "debug entry of decode_select: the kept set of every row as a (B, V) bool mask");
     m.def("decode_select_applicable", [](int64_t V) { return decode_select_applicable(V); },
           "host-only: whether decode_select has a tier for a vocabulary of V");
+    m.def("decode_attn", &decode_attn,
+          "single-query attention over the per-row key windows lo[b] .. hi[b] (inclusive, int64 "
+          "device tensors of 1 or B elements; lo None means 0)",
+          pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("lo"),
+          pybind11::arg("hi"));
+    m.def("decode_attn_applicable",
+          [](int64_t d, int64_t dv) { return decode_attn_applicable(d, dv); },
+          "host-only: whether decode_attn takes these head dims");
+    m.def("decode_attn_plan", &decode_attn_plan,
+          "host-only: (nsplit, row granule) of decode_attn's static grid (nsplit, H, B)");
     m.def("beam_select", &beam_select,
           "one beam-search step per group of num_beams rows: top-k of score + log-softmax with "
           "done / gen_len / token / parent bookkeeping",
