@@ -98,7 +98,7 @@ def allocate_kv_cache(model, batch: int, device=None, dtype=torch.float32,
 
     ``ca_capacity`` bounds the cross-attention cache below ``max_seq_len`` —
     the graph decoder reads the FULL capacity (masked) every step, so sizing
-    the cache to the actual sequence need (bucketed, see hf_base.generate)
+    the cache to the actual sequence need (bucketed, see graph_decode.capacity_bucket)
     cuts the dead-row KV traffic of short decodes.
     """
     def chans(layer):

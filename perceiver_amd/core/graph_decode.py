@@ -50,6 +50,13 @@ Design (vs. the host-driven path in ``PerceiverAR.forward``):
   keys; no mask tensor is built. The windows read ``counters`` and ``shift``,
   so one captured graph serves every padding pattern of its batch size.
 
+Which ``generate`` request replays a captured graph, and which cached decoder
+serves it, is decided at the bottom of this module and nowhere else:
+``graph_route`` is the one gate for token, beam and left-padded requests
+(``fits_graph``, ``left_padded`` and ``capacity_bucket`` are its pieces),
+``decoder_for`` is the one lookup in the model's ``_graph_decoders`` and
+``replay`` the one loop over ``decode``. ``models/hf_base.py`` only calls them.
+
 The un-captured step (``_step``) runs eagerly on any device, which is what the
 CPU numerics test compares against the host-driven cached forward. The reference
 has no equivalent (its cached decode is host-driven Python per token,
@@ -57,18 +64,18 @@ reference modules.py:820-871); this is MI355X-native serving machinery.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
+from perceiver_amd.core.cache import StaticKVCache, allocate_kv_cache
+from perceiver_amd.core.modules import MultiHeadAttention
+from perceiver_amd.core.position import RotaryPositionEmbedding
 from perceiver_amd.ops import beam as _beam
 from perceiver_amd.ops import sample as _sample
-from perceiver_amd.ops.decode_attn import KeyWindow
+from perceiver_amd.ops.decode_attn import KeyWindow, decode_attn_applicable
 
 _KEEP = object()  # set_sampling: leave this parameter as it is
-
-from perceiver_amd.core.cache import StaticKVCache
-from perceiver_amd.core.position import RotaryPositionEmbedding
 
 
 class GraphedDecoder:
@@ -193,9 +200,7 @@ class GraphedDecoder:
         src and the record row ``step_idx + rec_offset``. One launch on the GPU."""
         nb = self.num_beams
         if self.use_beam_kernel:
-            from perceiver_amd.ops import hip
-
-            hip.ext().beam_select(
+            _beam.beam_select_step(
                 logits, self.beam_scores, self.done, self.gen_len, self.tok.view(-1),
                 self.beam_src, self.group_done, self.eos_fill, nb, step=self.step_idx,
                 rec_offset=rec_offset, rec_tok=self.rec_tok, rec_parent=self.rec_parent,
@@ -312,32 +317,37 @@ class GraphedDecoder:
             # store keys pre-rotated at their absolute positions: the decode
             # step then never touches cached rows again (no O(cache) re-rotate)
             c.pre_rotated = True
-        n0 = prompt.shape[1]
-        prefix0 = prefix_len
+        n_ca, n_sa = prompt.shape[1], prompt.shape[1] - prefix_len
         pad_mask = self._left_pad_mask(prompt, attention_mask)
         if self.num_beams > 1:
-            return self._prefill_beams(prompt, prefix_len)
-        out = self.model(prompt, prefix_len=prefix_len, pad_mask=pad_mask, kv_cache=self.caches)
+            logits = self._prefill_beams(prompt, prefix_len)
+        else:
+            logits = self.model(prompt, prefix_len=prefix_len, pad_mask=pad_mask,
+                                kv_cache=self.caches).logits[:, -1, :]
 
-        self.ca_len.fill_(n0)
-        self.sa_len.fill_(n0 - prefix0)
+        self.ca_len.fill_(n_ca)
+        self.sa_len.fill_(n_sa)
         self.step_idx.fill_(0)
         self.draw_idx.fill_(0)
         self.done.zero_()
-        self._generator = None if self.use_kernel else generator  # torch composition only
-        if self.use_kernel:
-            if self._any_sample:  # greedy draws nothing
-                gdev = generator.device if generator is not None else "cpu"
-                self.seed.fill_(int(torch.randint(0, 2 ** 62, (1,), generator=generator,
-                                                  device=gdev).item()))
-        elif generator is not None and self.use_graph and self._any_sample:
-            raise RuntimeError("a generator on the captured-graph path needs the decode_select "
-                               "kernel (PERCEIVER_DECODE_SELECT=0 or an unsupported vocabulary)")
-        self._select_into_tok(out.logits[:, -1, :], record=False)
+        if self.num_beams > 1:
+            self._beam_select_into_tok(logits, rec_offset=0)
+        else:
+            self._generator = None if self.use_kernel else generator  # torch composition only
+            if self.use_kernel:
+                if self._any_sample:  # greedy draws nothing
+                    gdev = generator.device if generator is not None else "cpu"
+                    self.seed.fill_(int(torch.randint(0, 2 ** 62, (1,), generator=generator,
+                                                      device=gdev).item()))
+            elif generator is not None and self.use_graph and self._any_sample:
+                raise RuntimeError("a generator on the captured-graph path needs the "
+                                   "decode_select kernel (PERCEIVER_DECODE_SELECT=0 or an "
+                                   "unsupported vocabulary)")
+            self._select_into_tok(logits, record=False)
         self.draw_idx.fill_(1)
 
-        self.ca_len_host = n0
-        self.sa_len_host = n0 - prefix0
+        self.ca_len_host = n_ca
+        self.sa_len_host = n_sa
         self._steps_host = 0
         self.caches[0].enable_graph_append(self.ca_len)
         for c in self.caches[1:]:
@@ -358,18 +368,18 @@ class GraphedDecoder:
         if live.shape != prompt.shape:
             raise ValueError(f"attention_mask has shape {tuple(live.shape)}, the prompt "
                              f"{tuple(prompt.shape)}")
-        # 0…0 1…1: the last position is live and no live position precedes a pad
-        if not (bool(live[:, -1].all()) and bool((live[:, 1:] | ~live[:, :-1]).all())):
+        if not left_padded(live):
             raise ValueError("attention_mask must be left-padded (every row 0…0 1…1 with at "
                              "least one 1)")
         self.shift.copy_((~live).sum(dim=1))
         return ~live
 
     def _prefill_beams(self, prompt: torch.Tensor, prefix_len: int) -> torch.Tensor:
-        """Beam prefill: the ``bsz`` prompts run replicated, then beam 0's cache
-        rows and logits are broadcast over its group. A replicated batch through
-        library GEMMs is not guaranteed bit-identical row to row, and reordering
-        only the generated rows is exact only if the prompt rows are."""
+        """The beam middle of ``prefill``: the ``bsz`` prompts run replicated, then
+        beam 0's cache rows and logits are broadcast over its group. A replicated
+        batch through library GEMMs is not guaranteed bit-identical row to row,
+        and reordering only the generated rows is exact only if the prompt rows
+        are. Restarts the beam state and returns the (batch, vocab) logits."""
         nb, G = self.num_beams, self.groups
         if prompt.shape[0] != G:
             raise ValueError(f"beam prefill takes {G} prompts, got {prompt.shape[0]}")
@@ -385,11 +395,6 @@ class GraphedDecoder:
         logits = logits.view(G, nb, -1)[:, :1].expand(-1, nb, -1).reshape(G * nb, -1)
         self.last_logits = logits[:, None, :]
 
-        self.ca_len.fill_(n0)
-        self.sa_len.fill_(n0 - prefix0)
-        self.step_idx.fill_(0)
-        self.draw_idx.fill_(0)
-        self.done.zero_()
         self.gen_len.zero_()
         self.group_done.zero_()
         self.rec_all_done.zero_()
@@ -401,25 +406,14 @@ class GraphedDecoder:
             row0 = torch.tensor([n0 if ci == 0 else n0 - prefix0
                                  for ci in self._reorder_counter], dtype=torch.long)
             self.reorder_table[:, 4].copy_(row0)
-        self._beam_select_into_tok(logits, rec_offset=0)
-        self.draw_idx.fill_(1)
-
-        self.ca_len_host = n0
-        self.sa_len_host = n0 - prefix0
-        self._steps_host = 0
-        self.caches[0].enable_graph_append(self.ca_len)
-        for c in self.caches[1:]:
-            c.enable_graph_append(self.sa_len)
-        return self.tok.clone()
+        return logits
 
     def _select_into_tok(self, logits: torch.Tensor, record: bool):
         """tok <- next token from (batch, vocab) logits, with the EOS fill and
         ``done`` update; ``record`` first stores the previous token at the step
         cursor of ``out_buf``. One kernel launch on the GPU."""
         if self.use_kernel:
-            from perceiver_amd.ops import hip
-
-            hip.ext().decode_select(
+            _sample.select_step(
                 logits, self.p_do_sample, self.p_temperature, self.p_top_k, self.p_top_p,
                 self.seed, self.draw_idx, tok=self.tok.view(-1),
                 out_buf=self.out_buf if record else None,
@@ -563,3 +557,142 @@ class GraphedDecoder:
             return self.hypotheses()[:, s0 + 1:]
         first = self.out_buf[:, s0 + 1:s0 + n]
         return torch.cat([first, self.tok], dim=1)
+
+
+# ------------------------------------------------------------- request policy
+# Which generate() request replays a captured graph, and which cached decoder
+# serves it. ``model`` is the ``CausalSequenceModel`` backend throughout.
+
+class GraphRoute(NamedTuple):
+    """What ``graph_route`` grants a request."""
+
+    batch: int    # rows of the decoder's caches (bsz * num_beams)
+    bucket: int   # cross-attention cache capacity
+    ragged: bool  # a left-padded request: GraphedDecoder(ragged=True)
+    baked: bool   # torch selection: the sampling parameters are part of the graph
+
+
+def left_padded(attention_mask: torch.Tensor) -> bool:
+    """Whether every row of the (batch, n) mask is ``0…0 1…1`` with at least one
+    1: the last position is live and no live position precedes a pad."""
+    live = attention_mask != 0
+    return bool(live[:, -1].all()) and bool((live[:, 1:] | ~live[:, :-1]).all())
+
+
+def capacity_bucket(need: int, max_seq_len: int) -> int:
+    """Cross-attention cache capacity for a request of ``need`` positions: the
+    next power of two >= ``need`` (at least 2048), at most ``max_seq_len``. The
+    graphed step reads the FULL (masked) cache every token, so the cache is
+    sized to the request and not to the model (an 8192-context model would pay
+    8192 dead rows for a 1k-token request)."""
+    bucket = 2048
+    while bucket < need:
+        bucket *= 2
+    return min(bucket, max_seq_len)
+
+
+def fits_graph(model, seq_len: int, prefix_len: int, max_new_tokens: int,
+               eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None) -> bool:
+    """The shape half of ``graph_route``, the same for every mode: the capture
+    takes 2 steps after the prefill token, every generated token stays within
+    the latent-growth phase of the schedule (no prefix growth, no window
+    slide), and EOS / pad ids lie inside the vocabulary, because the graphed
+    step embeds the fill token where the host loop only writes it out."""
+    vocab = model.config.vocab_size
+    return (all(t is None or 0 <= t < vocab for t in (eos_token_id, pad_token_id))
+            and max_new_tokens >= 3
+            and (seq_len - prefix_len) + max_new_tokens <= model.max_latents
+            and seq_len + max_new_tokens <= model.max_seq_len)
+
+
+def graph_route(model, batch: int, seq_len: int, prefix_len: int, max_new_tokens: int,
+                num_beams: int = 1, attention_mask: Optional[torch.Tensor] = None,
+                eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
+                top_p: Optional[float] = None,
+                generator: Optional[torch.Generator] = None) -> Optional[GraphRoute]:
+    """THE gate of the captured-graph decode path: the route of a ``generate``
+    request, or None for one that keeps the host loop.
+
+    Every mode needs a GPU model and ``fits_graph``. On top of that:
+
+    - tokens (``num_beams == 1``): with the ``decode_select`` kernel every
+      sampling configuration replays one graph. Without it
+      (PERCEIVER_DECODE_SELECT=0, or a vocabulary it has no tier for) the torch
+      selection bakes ``do_sample`` / ``temperature`` / ``top_k`` into the
+      graph, and top-p, EOS and generator requests are refused.
+    - a mask that holds zeros: only left-padded, with the select kernel and
+      head dims that ``decode_attn`` takes in every attention layer. The
+      decoder is ragged then; unpadded requests keep a decoder of their own.
+    - beams: the beam kernels must apply (``2 <= num_beams <= 8``) and the mask
+      must hold no zero."""
+    p = next(model.parameters())
+    if p.device.type != "cuda" or not fits_graph(model, seq_len, prefix_len, max_new_tokens,
+                                                 eos_token_id, pad_token_id):
+        return None
+    vocab = model.config.vocab_size
+    padded = attention_mask is not None and bool((attention_mask == 0).any())
+    bucket = capacity_bucket(seq_len + max_new_tokens, model.max_seq_len)
+    if num_beams > 1:
+        if padded or not _beam.kernel_applicable(p.device, vocab, num_beams):
+            return None
+        return GraphRoute(batch * num_beams, bucket, ragged=False, baked=False)
+    select_kernel = _sample.kernel_applicable(p.device, vocab)
+    if not select_kernel and not (eos_token_id is None and top_p is None and generator is None):
+        return None
+    if padded and not (
+            select_kernel
+            and all(decode_attn_applicable(m.num_qk_channels // m.num_heads,
+                                           m.num_v_channels // m.num_heads)
+                    for m in model.modules() if isinstance(m, MultiHeadAttention))
+            and left_padded(attention_mask)):
+        return None
+    return GraphRoute(batch, bucket, ragged=padded, baked=not select_kernel)
+
+
+def decoder_for(owner, model, route: GraphRoute, num_beams: int = 1, do_sample=False,
+                temperature=1.0, top_k=None, make=GraphedDecoder) -> GraphedDecoder:
+    """The decoder (captured graph + caches) that serves ``route``, kept in the
+    plain dict ``owner._graph_decoders``: repeated requests only pay prefill +
+    replays. At most two are held, token and beam decoders alike, and the
+    oldest goes first, which bounds the cache memory. ``make`` is
+    ``GraphedDecoder`` except in tests.
+
+    ``p.data_ptr()`` pins a cached graph to the current parameter storage:
+    ``model.to(device/dtype)`` reallocates it, and a graph replaying against the
+    old pointers would silently use stale weights (an in-place
+    ``load_state_dict`` is fine, the graph holds parameter pointers)."""
+    p = next(model.parameters())
+    key = (route.batch, route.bucket, p.device, p.dtype, p.data_ptr(), num_beams, route.ragged)
+    if route.baked:
+        key += (do_sample, float(temperature), top_k)
+    cache = getattr(owner, "_graph_decoders", None)
+    if cache is None:
+        cache = owner._graph_decoders = {}
+    gd = cache.get(key)
+    if gd is None:
+        if len(cache) >= 2:
+            cache.pop(next(iter(cache)))
+        gd = cache[key] = make(
+            model, allocate_kv_cache(model, route.batch, device=p.device, dtype=p.dtype,
+                                     ca_capacity=route.bucket),
+            do_sample=do_sample, temperature=temperature, top_k=top_k, num_beams=num_beams,
+            ragged=route.ragged)
+    return gd
+
+
+def replay(gd: GraphedDecoder, n: int, eos_token_id: Optional[int] = None,
+           tokens: bool = True) -> Optional[torch.Tensor]:
+    """Decode up to ``n`` tokens after ``gd.prefill``. Without EOS that is one
+    ``decode(n)`` with no host synchronisation. With EOS the replays run in
+    chunks of 16 with one look at ``finished`` between them (one sync per 16
+    tokens) and stop once every row is done; the caller cuts the result where
+    the host loop would have stopped. Returns (batch, <= n) tokens, or None
+    with ``tokens=False``."""
+    if eos_token_id is None:
+        return gd.decode(n, tokens=tokens)
+    chunks = [gd.tok[:, :0]]
+    while n > 0 and not bool(gd.finished.all()):
+        c = min(16, n)
+        chunks.append(gd.decode(c, tokens=tokens))
+        n -= c
+    return torch.cat(chunks, dim=1) if tokens else None

@@ -27,6 +27,7 @@ from perceiver_amd.core import (
     PerceiverEncoder,
     SelfAttentionLayer,
 )
+from perceiver_amd.core import graph_decode as _graph
 from perceiver_amd.core.cache import StaticKVCache, allocate_kv_cache, cache_len
 from perceiver_amd.core.modules import KVCache
 
@@ -290,98 +291,29 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
         done = torch.zeros(input_ids.shape[0], dtype=torch.bool, device=input_ids.device)
         past = None
         if use_cache and static_cache:
-            p = next(self.backend_model.parameters())
-
-            # hipGraph fast path: when every generated token stays within the
-            # latent-growth phase of the schedule (no prefix growth/window
-            # slide), decode is one captured-graph replay per token. Token
-            # selection is the decode_select kernel, which reads temperature,
-            # top-k, top-p, EOS and the seed from device buffers: greedy,
-            # sampled, nucleus, EOS-stopped and seeded requests all replay the
-            # same graph. Decoders (captured graph + caches) are cached per
-            # batch size — repeated serving requests only pay prefill +
-            # replays. Weight updates are fine (the graph holds parameter
-            # pointers). Without the kernel (PERCEIVER_DECODE_SELECT=0, or a
-            # vocabulary it has no tier for) the torch selection bakes its
-            # parameters into the graph, and top-p, EOS and generator requests
-            # take the host loop below.
-            from perceiver_amd.ops import sample as _sample
-
-            vocab = self.backend_model.config.vocab_size
-            select_kernel = _sample.kernel_applicable(p.device, vocab)
-            # the graphed step embeds the fill token: ids outside the
-            # vocabulary stay on the host loop, which only writes them out
-            ids_ok = all(t is None or 0 <= t < vocab for t in (eos_token_id, pad_token_id))
-            # a left-padded batch decodes on a ragged decoder (per-row key
-            # windows, ops/decode_attn.py); any other padding keeps the host loop
-            padded = p.device.type == "cuda" and bool((attention_mask == 0).any())
-            if (p.device.type == "cuda" and ids_ok
-                    and (select_kernel or (eos_token_id is None and top_p is None
-                                           and generator is None))
-                    and max_new_tokens >= 3
-                    and (seq_len - prefix_len) + max_new_tokens <= self.backend_model.max_latents
-                    and seq_len + max_new_tokens <= self.backend_model.max_seq_len
-                    and (not padded or self._ragged_graph_ok(attention_mask, select_kernel))):
-                from perceiver_amd.core.graph_decode import GraphedDecoder
-
-                ragged = padded  # unpadded requests keep their decoder and cache key
-
-                # bucketed cache capacity: the graphed step reads the FULL
-                # (masked) CA cache every token, so size it to the request —
-                # the next power-of-two bucket >= seq_len + max_new_tokens
-                # (>= 2048) instead of always max_seq_len (8192-ctx models
-                # were paying 8192 dead rows for 1k-token requests)
-                need = seq_len + max_new_tokens
-                bucket = 2048
-                while bucket < need:
-                    bucket *= 2
-                bucket = min(bucket, self.backend_model.max_seq_len)
-
-                # p.data_ptr() pins the cached graphs to the current parameter
-                # storage: model.to(device/dtype) reallocates storage, and a
-                # captured graph replaying against the old pointers would
-                # silently use stale weights (in-place load_state_dict is fine)
-                key = (input_ids.shape[0], bucket, p.device, p.dtype, p.data_ptr())
-                if not select_kernel:  # baked into the graph on the torch path
-                    key += (do_sample, float(temperature), top_k)
-                if ragged:
-                    key += ("ragged",)
-                cache = getattr(self, "_graph_decoders", None)
-                if cache is None:
-                    cache = self._graph_decoders = {}
-                gd = cache.get(key)
-                if gd is None:
-                    if len(cache) >= 2:  # bound held cache memory
-                        cache.pop(next(iter(cache)))
-                    gd = cache[key] = GraphedDecoder(
-                        self.backend_model,
-                        allocate_kv_cache(self.backend_model, input_ids.shape[0],
-                                          device=p.device, dtype=p.dtype,
-                                          ca_capacity=bucket),
-                        do_sample=do_sample, temperature=temperature, top_k=top_k,
-                        ragged=ragged)
-                if select_kernel:
+            # hipGraph fast path: one captured-graph replay per token for the
+            # requests that graph_decode.graph_route admits
+            route = _graph.graph_route(
+                self.backend_model, input_ids.shape[0], seq_len, prefix_len, max_new_tokens,
+                attention_mask=attention_mask, eos_token_id=eos_token_id,
+                pad_token_id=pad_token_id, top_p=top_p, generator=generator)
+            if route is not None:
+                gd = _graph.decoder_for(self, self.backend_model, route, do_sample=do_sample,
+                                        temperature=temperature, top_k=top_k)
+                if not route.baked:
                     gd.set_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k,
                                     top_p=top_p, eos_token_id=eos_token_id,
                                     pad_token_id=pad_token_id)
                 first = gd.prefill(input_ids, prefix_len=prefix_len, generator=generator,
-                                   attention_mask=attention_mask if ragged else None)
-                if eos_token_id is None:
-                    rest = gd.decode(max_new_tokens - 1)
-                    return torch.cat([input_ids, first, rest], dim=1)
-                # EOS: replay in chunks of 16 and look at the done mask between
-                # them (one sync per 16 tokens), then cut where the host loop
-                # would have stopped: after the first step at which every row
-                # is done
-                new, left = [first], max_new_tokens - 1
-                while left > 0 and not bool(gd.finished.all()):
-                    n = min(16, left)
-                    new.append(gd.decode(n))
-                    left -= n
-                new = self._cut_at_all_done(torch.cat(new, dim=1), eos_token_id)
+                                   attention_mask=attention_mask if route.ragged else None)
+                new = torch.cat([first, _graph.replay(gd, max_new_tokens - 1, eos_token_id)],
+                                dim=1)
+                if eos_token_id is not None:  # cut where the host loop would have stopped
+                    new = self._cut_at_all_done(new, eos_token_id)
                 return torch.cat([input_ids, new], dim=1)
 
             # preallocated in-place cache: no per-step concat/realloc (K9)
+            p = next(self.backend_model.parameters())
             past = allocate_kv_cache(self.backend_model, input_ids.shape[0],
                                      device=p.device, dtype=p.dtype)
 
@@ -410,80 +342,28 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
 
         return input_ids
 
-    def _ragged_graph_ok(self, attention_mask, select_kernel: bool) -> bool:
-        """Whether a request whose mask holds zeros may take the graph path: every
-        row left-padded (``0…0 1…1`` with at least one 1), the select kernel
-        applies, and ``decode_attn`` takes every attention layer's head dims.
-        Right padding, holes and all-zero rows keep the host loop."""
-        from perceiver_amd.ops.decode_attn import decode_attn_applicable
-
-        if not select_kernel:
-            return False
-        for m in self.backend_model.modules():
-            if isinstance(m, MultiHeadAttention) and not decode_attn_applicable(
-                    m.num_qk_channels // m.num_heads, m.num_v_channels // m.num_heads):
-                return False
-        live = attention_mask != 0
-        return bool(live[:, -1].all()) and bool((live[:, 1:] | ~live[:, :-1]).all())
-
     @torch.no_grad()
     def _beam_search_graphed(self, input_ids, attention_mask, prefix_len, num_beams,
                              max_new_tokens, eos_token_id, pad_token_id, length_penalty):
-        """Beam search on the captured decode graph, under the gating greedy has
-        (GPU, kernels applicable, no padding, ids inside the vocabulary, at least
-        3 new tokens, the request inside the latent-growth phase) plus
-        ``2 <= num_beams <= 8``. Returns None when the request is outside the
-        gate: the host loop ``_beam_search`` runs then.
+        """Beam search on the captured decode graph. Returns None when
+        ``graph_decode.graph_route`` refuses the request: the host loop
+        ``_beam_search`` runs then.
 
         One decoder (captured graph + caches of ``bsz * num_beams`` rows) is kept
         per (bsz, num_beams, bucket); EOS and fill ids live in device memory, so
         requests that differ in them or in prompt length replay the same graph."""
-        from perceiver_amd.ops import beam as _beam
-
-        bm = self.backend_model
-        p = next(bm.parameters())
-        vocab = bm.config.vocab_size
         bsz, seq_len = input_ids.shape
-        ids_ok = all(t is None or 0 <= t < vocab for t in (eos_token_id, pad_token_id))
-        if not (p.device.type == "cuda" and ids_ok
-                and _beam.kernel_applicable(p.device, vocab, num_beams)
-                and not bool((attention_mask == 0).any())
-                and max_new_tokens >= 3
-                and (seq_len - prefix_len) + max_new_tokens <= bm.max_latents
-                and seq_len + max_new_tokens <= bm.max_seq_len):
+        route = _graph.graph_route(
+            self.backend_model, bsz, seq_len, prefix_len, max_new_tokens, num_beams=num_beams,
+            attention_mask=attention_mask, eos_token_id=eos_token_id, pad_token_id=pad_token_id)
+        if route is None:
             return None
-        from perceiver_amd.core.graph_decode import GraphedDecoder
-
-        need = seq_len + max_new_tokens
-        bucket = 2048
-        while bucket < need:
-            bucket *= 2
-        bucket = min(bucket, bm.max_seq_len)
-        key = (bsz * num_beams, bucket, p.device, p.dtype, p.data_ptr(), num_beams)
-        cache = getattr(self, "_graph_decoders", None)
-        if cache is None:
-            cache = self._graph_decoders = {}
-        gd = cache.get(key)
-        if gd is None:
-            if len(cache) >= 2:  # bound held cache memory
-                cache.pop(next(iter(cache)))
-            gd = cache[key] = GraphedDecoder(
-                bm, allocate_kv_cache(bm, bsz * num_beams, device=p.device, dtype=p.dtype,
-                                      ca_capacity=bucket),
-                num_beams=num_beams)
+        gd = _graph.decoder_for(self, self.backend_model, route, num_beams=num_beams)
         # the host loop's fill: the pad id, else EOS, else 0
         gd.set_sampling(eos_token_id=eos_token_id, pad_token_id=pad_token_id)
         gd.prefill(input_ids, prefix_len=prefix_len)
-        left = max_new_tokens - 1
-        if eos_token_id is None:
-            gd.decode(left, tokens=False)
-        else:
-            # chunks of 16 with one look at the done mask in between; best() cuts
-            # the output where the host loop would have stopped
-            while left > 0 and not bool(gd.finished.all()):
-                n = min(16, left)
-                gd.decode(n, tokens=False)
-                left -= n
+        _graph.replay(gd, max_new_tokens - 1, eos_token_id, tokens=False)
+        # best() cuts the output where the host loop would have stopped
         tokens, _ = gd.best(length_penalty)
         return torch.cat([input_ids, tokens], dim=1)
 

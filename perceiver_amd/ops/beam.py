@@ -80,6 +80,22 @@ def beam_select_reference(logits: torch.Tensor, scores: torch.Tensor, done: torc
             new_done.view(G, nb).all(-1))
 
 
+def beam_select_step(logits: torch.Tensor, scores: torch.Tensor, done: torch.Tensor,
+                     gen_len: torch.Tensor, tok: torch.Tensor, src: torch.Tensor,
+                     all_done: torch.Tensor, eos_fill: torch.Tensor, num_beams: int, *,
+                     step: torch.Tensor, rec_offset: int, rec_tok: torch.Tensor,
+                     rec_parent: torch.Tensor, rec_all_done: torch.Tensor):
+    """Launch one beam step in place: ``scores``, ``done``, ``gen_len`` (int32),
+    ``tok`` (int64), ``src`` (int32), all (G * num_beams,), and ``all_done`` (G,)
+    take the results ``beam_select_reference`` returns, with ``eos_fill`` the
+    int64 pair ``[eos, fill]``. Row ``step + rec_offset`` of the records
+    ``rec_tok`` / ``rec_parent`` / ``rec_all_done`` takes ``tok`` / ``src`` /
+    ``all_done``; ``step`` is one int64 on the device."""
+    hip.ext().beam_select(logits, scores, done, gen_len, tok, src, all_done, eos_fill,
+                          int(num_beams), step=step, rec_offset=rec_offset, rec_tok=rec_tok,
+                          rec_parent=rec_parent, rec_all_done=rec_all_done)
+
+
 REORDER_FIELDS = 6
 
 

@@ -139,3 +139,18 @@ def select_tokens(logits: torch.Tensor, *, do_sample: Param = False, temperature
     g = torch.Generator(device=dev)
     g.manual_seed((int(seed) * 1000003 + int(draw)) % (2 ** 63))
     return select_reference(logits, do_sample, temperature, top_k, top_p, g)
+
+
+def select_step(logits: torch.Tensor, do_sample: torch.Tensor, temperature: torch.Tensor,
+                top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor, draw: torch.Tensor,
+                *, tok: torch.Tensor, done: torch.Tensor, eos_fill: torch.Tensor,
+                out_buf: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None):
+    """One in-place decode step, the launch a captured graph replays. Every
+    argument is a device buffer in the kernel's own dtype (the (B,) parameters
+    as ``row_param`` makes them, ``seed`` / ``draw`` / ``step`` one int64 each).
+    With ``out_buf`` and ``step`` the previous ``tok`` is first recorded at
+    column ``step`` of ``out_buf``; then ``tok`` (B,) takes the selected token,
+    or the fill of ``eos_fill = [eos, fill]`` on a ``done`` row, and ``done``
+    takes the rows that emitted EOS."""
+    hip.ext().decode_select(logits, do_sample, temperature, top_k, top_p, seed, draw, tok=tok,
+                            out_buf=out_buf, step=step, done=done, eos_fill=eos_fill)
