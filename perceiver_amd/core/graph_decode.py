@@ -39,6 +39,16 @@ Design (vs. the host-driven path in ``PerceiverAR.forward``):
   The prompt rows of a group's beams are bit-identical copies of one prefill,
   so only the generated rows ever move. Each step records (token, parent);
   the histories are backtracked once, after the replays (``ops/beam.py``).
+- Contrastive search (``contrastive_k=k``): the caches hold ``bsz * k`` rows,
+  the k candidates of a prompt in consecutive rows, and the step ends with
+  three launches (``ops/contrastive.py``): ``contrastive_sim`` (max cosine of
+  the k candidate hidden states against the group's history, whose length is
+  ``sa_len``), ``contrastive_commit`` (score, select, record, append to the
+  history, propose the next k candidates) and ``contrastive_copy`` (the
+  winner's freshly appended KV row goes to the group's other rows: O(1) rows
+  per step). Invariant: at every step boundary the k rows of a group hold
+  bit-identical cache rows ``[0, len)``, so no candidate ever needs a cache of
+  its own. ``penalty_alpha``, EOS and fill ids are device buffers.
 - Left-padded prompt batches (``ragged=True``): ``prefill`` takes an
   ``attention_mask`` whose rows are ``0…0 1…1`` and stores each row's pad count
   in the device buffer ``shift``. The step then states the live keys of every
@@ -52,7 +62,7 @@ Design (vs. the host-driven path in ``PerceiverAR.forward``):
 
 Which ``generate`` request replays a captured graph, and which cached decoder
 serves it, is decided at the bottom of this module and nowhere else:
-``graph_route`` is the one gate for token, beam and left-padded requests
+``graph_route`` is the one gate for token, beam, contrastive and left-padded requests
 (``fits_graph``, ``left_padded`` and ``capacity_bucket`` are its pieces),
 ``decoder_for`` is the one lookup in the model's ``_graph_decoders`` and
 ``replay`` the one loop over ``decode``. ``models/hf_base.py`` only calls them.
@@ -72,6 +82,7 @@ from perceiver_amd.core.cache import StaticKVCache, allocate_kv_cache
 from perceiver_amd.core.modules import MultiHeadAttention
 from perceiver_amd.core.position import RotaryPositionEmbedding
 from perceiver_amd.ops import beam as _beam
+from perceiver_amd.ops import contrastive as _contrastive
 from perceiver_amd.ops import sample as _sample
 from perceiver_amd.ops.decode_attn import KeyWindow, decode_attn_applicable
 
@@ -94,13 +105,21 @@ class GraphedDecoder:
                  do_sample: bool = False, temperature: float = 1.0,
                  top_k: Optional[int] = None, top_p: Optional[float] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
-                 num_beams: int = 1, ragged: bool = False):
+                 num_beams: int = 1, ragged: bool = False, contrastive_k: int = 0,
+                 penalty_alpha: float = 0.6):
         """``ragged``: ``prefill`` accepts a left-padded ``attention_mask`` and the
         step attends per-row key windows (module docstring). Not with beams.
         ``num_beams > 1``: beam search. The caches' batch is ``bsz * num_beams``
         (beams of one prompt are consecutive rows), ``prefill`` takes the ``bsz``
         prompts, the sampling parameters are unused and ``best`` returns the
         winning hypotheses.
+        ``contrastive_k > 0``: contrastive search over the top ``contrastive_k``
+        tokens with degeneration penalty ``penalty_alpha``. The caches' batch is
+        ``bsz * contrastive_k``, ``prefill`` takes the ``bsz`` prompts and returns
+        the first (bsz, k) candidates, ``decode`` returns (bsz, n) committed
+        tokens and ``finished`` is (bsz,). Not with ``ragged`` or beams. At every
+        step boundary the k rows of a group hold bit-identical cache rows
+        ``[0, len)``.
         ``do_sample``: in-graph ancestral sampling (temperature scaling,
         optional top-k and top-p truncation). On the GPU the selection is the
         ``decode_select`` kernel with a counter-hash draw keyed by a per-prefill
@@ -111,6 +130,9 @@ class GraphedDecoder:
         if ragged and int(num_beams) > 1:
             raise ValueError("ragged=True with num_beams > 1: padded beam requests are not "
                              "supported by the graphed decoder")
+        if int(contrastive_k) > 0 and (ragged or int(num_beams) > 1):
+            raise ValueError("contrastive_k with ragged=True or num_beams > 1: contrastive "
+                             "search runs unpadded and without beams on the graphed decoder")
         self.model = model
         self.caches = caches
         self.ragged = bool(ragged)
@@ -160,8 +182,12 @@ class GraphedDecoder:
         self.num_beams = int(num_beams)
         if self.num_beams > 1:
             self._init_beams()
+        self.contrastive_k = int(contrastive_k)
+        if self.contrastive_k > 0:
+            self._init_contrastive()
         self.do_sample, self.temperature, self.top_k, self.top_p = False, 1.0, None, None
         self.eos_token_id = self.pad_token_id = None
+        self.penalty_alpha = float(penalty_alpha)
         self.set_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k,
                           top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id)
 
@@ -248,16 +274,127 @@ class GraphedDecoder:
             toks = toks[:, :int(stop.int().argmax()) + 1]
         return toks, scores.gather(1, pick[:, None]).squeeze(1)
 
+    # -------------------------------------------------------------- contrastive
+
+    def _init_contrastive(self):
+        k, B, dev = self.contrastive_k, self.batch, self.device
+        if not (_contrastive.MIN_K <= k <= _contrastive.MAX_K and k <= self.vocab):
+            raise ValueError(f"contrastive_k={k} / vocabulary {self.vocab} outside the "
+                             f"contrastive decoder's range")
+        if B % k:
+            raise ValueError(f"cache batch {B} is not a multiple of contrastive_k={k}")
+        self.groups = B // k
+        C = self.model.config.num_channels
+        # decided once, like use_kernel: a captured graph holds whichever step it was built with
+        self.use_contrastive_kernel = _contrastive.kernel_applicable(dev, self.vocab, k, C,
+                                                                     self.dtype)
+        # the history: bit copies of the hidden states the model produced (the
+        # prompt's latent positions, then one row per committed step) and their
+        # reciprocal norms; its length is sa_len
+        rows = self.sa_cap or self.ca_cap
+        self.hist = torch.zeros(self.groups, rows, C, dtype=self.dtype, device=dev)
+        self.hist_rnorm = torch.zeros(self.groups, rows, dtype=torch.float32, device=dev)
+        self.cand_prob = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.cand_src = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.alpha = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.done = torch.zeros(self.groups, dtype=torch.bool, device=dev)
+        # row r: the token committed by step r; the last step's similarities and scores
+        self.rec_tok = torch.zeros(rows + 1, self.groups, dtype=torch.long, device=dev)
+        self.last_sim = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.last_score = torch.zeros(B, dtype=torch.float32, device=dev)
+        self._reorder_bufs = [b for c in self.caches for b in (c.k_buf, c.v_buf)]
+        self._reorder_counter = [0 if i == 0 else 1 for i, c in enumerate(self.caches)
+                                 for _ in range(2)]
+        self.reorder_table = None
+        if self.use_contrastive_kernel:
+            self.reorder_table = _beam.reorder_table(
+                self._reorder_bufs, [0] * len(self._reorder_bufs), self._reorder_counter).to(dev)
+
+    def _prefill_contrastive(self, prompt: torch.Tensor, prefix_len: int) -> torch.Tensor:
+        """The contrastive middle of ``prefill``: the ``bsz`` prompts run replicated,
+        then row 0's cache rows and logits are broadcast over its group (as
+        ``_prefill_beams`` does, for the same reason) and the history is filled
+        from row 0's latent hidden states. Returns the (batch, vocab) logits."""
+        k, G = self.contrastive_k, self.groups
+        if prompt.shape[0] != G:
+            raise ValueError(f"contrastive prefill takes {G} prompts, got {prompt.shape[0]}")
+        n0, n_sa = prompt.shape[1], prompt.shape[1] - prefix_len
+        out = self.model(prompt.repeat_interleave(k, dim=0), prefix_len=prefix_len,
+                         kv_cache=self.caches)
+        for i, c in enumerate(self.caches):
+            n = n0 if i == 0 else n_sa
+            for buf in (c.k_buf, c.v_buf):
+                v = buf.view(G, k, *buf.shape[1:])
+                v[:, 1:, :n].copy_(v[:, :1, :n].expand(-1, k - 1, -1, -1))
+        hs = out.last_hidden_state.reshape(G, k, n_sa, -1)[:, 0]
+        self.hist[:, :n_sa].copy_(hs)
+        self.hist_rnorm[:, :n_sa].copy_(_contrastive.recip_norm(hs))
+        logits = out.logits[:, -1, :]
+        logits = logits.view(G, k, -1)[:, :1].expand(-1, k, -1).reshape(G * k, -1)
+        self.last_logits = logits[:, None, :]
+        return logits
+
+    def _propose_into_tok(self, logits: torch.Tensor):
+        """tok, cand_prob <- the k candidates of row 0 of every group of the
+        (batch, vocab) logits. One launch on the GPU."""
+        k = self.contrastive_k
+        if self.use_contrastive_kernel:
+            _contrastive.propose_step(logits, self.tok.view(-1), self.cand_prob, k)
+            return
+        tok, prob = _contrastive.propose_reference(logits.view(self.groups, k, -1)[:, 0], k)
+        self.tok.copy_(tok.reshape(-1, 1))
+        self.cand_prob.copy_(prob.reshape(-1))
+
+    def _contrastive_commit(self, h: torch.Tensor, logits: torch.Tensor):
+        """One contrastive step from the (batch, C) candidate hidden states and
+        their (batch, vocab) logits: record row ``step_idx``, done, the history
+        row ``sa_len``, the next candidates and the copy of the winner's new KV
+        row over its group. Three launches on the GPU."""
+        k, G = self.contrastive_k, self.groups
+        if self.use_contrastive_kernel:
+            part = _contrastive.contrastive_sim(h, self.hist, self.hist_rnorm, self.sa_len, k)
+            _contrastive.commit_step(
+                logits, self.tok.view(-1), self.cand_prob, k, h=h, part=part, hist=self.hist,
+                rnorm=self.hist_rnorm, hist_len=self.sa_len, done=self.done, src=self.cand_src,
+                alpha=self.alpha, eos_fill=self.eos_fill, step=self.step_idx, rec=self.rec_tok,
+                sim_out=self.last_sim, score_out=self.last_score)
+            _contrastive.contrastive_copy(self.reorder_table, self.counters, self.cand_src, k,
+                                          buffers=self._reorder_bufs)
+            return
+        sel, emitted, done, sim, score = _contrastive.contrastive_reference(
+            h, self.hist, self.hist_rnorm, self.sa_len, self.tok.view(-1), self.cand_prob,
+            self.done, self.alpha[0], self.eos_fill[0], self.eos_fill[1], k)
+        rows = sel + torch.arange(G, device=self.device) * k
+        self.rec_tok.index_copy_(0, self.step_idx, emitted[None])
+        self.done.copy_(done)
+        self.cand_src.copy_(sel.repeat_interleave(k))
+        self.last_sim.copy_(sim.reshape(-1))
+        self.last_score.copy_(score.reshape(-1))
+        won = h.index_select(0, rows)
+        at = self.sa_len.clamp(max=self.hist.shape[1] - 1)
+        self.hist.index_copy_(1, at, won[:, None].to(self.hist.dtype))
+        self.hist_rnorm.index_copy_(1, at, _contrastive.recip_norm(won)[:, None])
+        tok, prob = _contrastive.propose_reference(logits.index_select(0, rows), k)
+        self.tok.copy_(tok.reshape(-1, 1))
+        self.cand_prob.copy_(prob.reshape(-1))
+        _contrastive.copy_reference(
+            self._reorder_bufs, [self.counters[ci:ci + 1] for ci in self._reorder_counter], sel, k)
+
     # ----------------------------------------------------------------- sampling
 
     def set_sampling(self, do_sample=_KEEP, temperature=_KEEP, top_k=_KEEP, top_p=_KEEP,
-                     eos_token_id=_KEEP, pad_token_id=_KEEP):
+                     eos_token_id=_KEEP, pad_token_id=_KEEP, penalty_alpha=_KEEP):
         """Rewrite the sampling parameters between requests. ``do_sample``,
         ``temperature``, ``top_k`` and ``top_p`` take scalars or per-row
         ``(batch,)`` tensors; None switches top-k / top-p / EOS off. With the
         kernel the captured graph is reused as it is. The torch composition
         bakes the values into the graph, so there a change drops the graph and
-        the next ``decode`` captures again."""
+        the next ``decode`` captures again. ``penalty_alpha`` (a contrastive
+        decoder's) is a device buffer in both forms, like EOS and fill."""
+        if penalty_alpha is not _KEEP:
+            self.penalty_alpha = float(penalty_alpha)
+        if self.contrastive_k:
+            self.alpha.fill_(self.penalty_alpha)
         if do_sample is not _KEEP:
             self.do_sample = do_sample
         if temperature is not _KEEP:
@@ -285,12 +422,14 @@ class GraphedDecoder:
         self.eos_fill.copy_(torch.tensor([self._eos, self._fill], dtype=torch.long))
         ds = self.do_sample
         self._any_sample = bool(ds.any()) if isinstance(ds, torch.Tensor) else bool(ds)
-        if not self.use_kernel and self.num_beams == 1:  # the beam step reads eos_fill itself
+        # the beam and the contrastive steps read eos_fill themselves
+        if not self.use_kernel and self.num_beams == 1 and not self.contrastive_k:
             self._graph = None
 
     @property
     def finished(self) -> torch.Tensor:
-        """(batch,) bool: rows that have emitted ``eos_token_id`` since the prefill."""
+        """(batch,) bool: rows that have emitted ``eos_token_id`` since the prefill
+        ((bsz,) for a contrastive decoder: one flag per prompt)."""
         return self.done
 
     # ------------------------------------------------------------------ prefill
@@ -300,7 +439,8 @@ class GraphedDecoder:
                 generator: Optional[torch.Generator] = None,
                 attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run the normal host-driven cached forward over the prompt, seed the
-        device counters/buffers, and return the first selected token.
+        device counters/buffers, and return the first selected token (a
+        contrastive decoder: the first (bsz, k) candidates).
 
         ``attention_mask`` (a ``ragged`` decoder only): (batch, n) with every row
         ``0…0 1…1`` and at least one 1, anything else raises ``ValueError``. The
@@ -321,6 +461,8 @@ class GraphedDecoder:
         pad_mask = self._left_pad_mask(prompt, attention_mask)
         if self.num_beams > 1:
             logits = self._prefill_beams(prompt, prefix_len)
+        elif self.contrastive_k:
+            logits = self._prefill_contrastive(prompt, prefix_len)
         else:
             logits = self.model(prompt, prefix_len=prefix_len, pad_mask=pad_mask,
                                 kv_cache=self.caches).logits[:, -1, :]
@@ -332,6 +474,8 @@ class GraphedDecoder:
         self.done.zero_()
         if self.num_beams > 1:
             self._beam_select_into_tok(logits, rec_offset=0)
+        elif self.contrastive_k:
+            self._propose_into_tok(logits)
         else:
             self._generator = None if self.use_kernel else generator  # torch composition only
             if self.use_kernel:
@@ -352,6 +496,8 @@ class GraphedDecoder:
         self.caches[0].enable_graph_append(self.ca_len)
         for c in self.caches[1:]:
             c.enable_graph_append(self.sa_len)
+        if self.contrastive_k:
+            return self.tok.view(self.groups, self.contrastive_k).clone()
         return self.tok.clone()
 
     def _left_pad_mask(self, prompt, attention_mask) -> Optional[torch.Tensor]:
@@ -501,6 +647,8 @@ class GraphedDecoder:
         if self.num_beams > 1:
             self._beam_select_into_tok(logits[:, -1, :], rec_offset=1)
             self._beam_reorder()
+        elif self.contrastive_k:
+            self._contrastive_commit(h[:, -1, :], logits[:, -1, :])
         else:
             self._select_into_tok(logits[:, -1, :], record=True)
         self.counters.add_(1)  # cache lengths, step cursor and draw index together
@@ -520,8 +668,8 @@ class GraphedDecoder:
 
     @torch.no_grad()
     def decode(self, n: int, tokens: bool = True) -> Optional[torch.Tensor]:
-        """Generate the next ``n`` tokens after ``prefill``; returns (batch, n),
-        or None with ``tokens=False`` (a beam caller that only wants ``best``
+        """Generate the next ``n`` tokens after ``prefill``; returns (batch, n)
+        ((bsz, n) committed tokens for a contrastive decoder), or None with ``tokens=False`` (a beam caller that only wants ``best``
         spares the backtrack).
         May be called repeatedly after one prefill (``generate`` decodes in
         chunks to look at ``finished`` in between). The first call captures the
@@ -555,6 +703,8 @@ class GraphedDecoder:
         if self.num_beams > 1:
             # the current beams' last n tokens; a later step may still permute them
             return self.hypotheses()[:, s0 + 1:]
+        if self.contrastive_k:
+            return self.rec_tok[s0:s0 + n].t().contiguous()
         first = self.out_buf[:, s0 + 1:s0 + n]
         return torch.cat([first, self.tok], dim=1)
 
@@ -609,7 +759,8 @@ def graph_route(model, batch: int, seq_len: int, prefix_len: int, max_new_tokens
                 num_beams: int = 1, attention_mask: Optional[torch.Tensor] = None,
                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
                 top_p: Optional[float] = None,
-                generator: Optional[torch.Generator] = None) -> Optional[GraphRoute]:
+                generator: Optional[torch.Generator] = None,
+                contrastive_k: int = 0) -> Optional[GraphRoute]:
     """THE gate of the captured-graph decode path: the route of a ``generate``
     request, or None for one that keeps the host loop.
 
@@ -624,7 +775,11 @@ def graph_route(model, batch: int, seq_len: int, prefix_len: int, max_new_tokens
       head dims that ``decode_attn`` takes in every attention layer. The
       decoder is ragged then; unpadded requests keep a decoder of their own.
     - beams: the beam kernels must apply (``2 <= num_beams <= 8``) and the mask
-      must hold no zero."""
+      must hold no zero.
+    - contrastive search (``contrastive_k > 0``; ``generate`` sends only
+      requests that do not sample): no zero in the mask, and the contrastive kernels must apply (``2 <= k <= 8``, bf16
+      hidden states of a multiple of 8 channels, PERCEIVER_CONTRASTIVE_GRAPH
+      not 0). The route's batch is ``batch * k``."""
     p = next(model.parameters())
     if p.device.type != "cuda" or not fits_graph(model, seq_len, prefix_len, max_new_tokens,
                                                  eos_token_id, pad_token_id):
@@ -636,6 +791,11 @@ def graph_route(model, batch: int, seq_len: int, prefix_len: int, max_new_tokens
         if padded or not _beam.kernel_applicable(p.device, vocab, num_beams):
             return None
         return GraphRoute(batch * num_beams, bucket, ragged=False, baked=False)
+    if contrastive_k > 0:
+        if padded or not _contrastive.kernel_applicable(
+                p.device, vocab, contrastive_k, model.config.num_channels, p.dtype):
+            return None
+        return GraphRoute(batch * contrastive_k, bucket, ragged=False, baked=False)
     select_kernel = _sample.kernel_applicable(p.device, vocab)
     if not select_kernel and not (eos_token_id is None and top_p is None and generator is None):
         return None
@@ -650,19 +810,22 @@ def graph_route(model, batch: int, seq_len: int, prefix_len: int, max_new_tokens
 
 
 def decoder_for(owner, model, route: GraphRoute, num_beams: int = 1, do_sample=False,
-                temperature=1.0, top_k=None, make=GraphedDecoder) -> GraphedDecoder:
+                temperature=1.0, top_k=None, make=GraphedDecoder,
+                contrastive_k: int = 0) -> GraphedDecoder:
     """The decoder (captured graph + caches) that serves ``route``, kept in the
     plain dict ``owner._graph_decoders``: repeated requests only pay prefill +
     replays. At most two are held, token and beam decoders alike, and the
     oldest goes first, which bounds the cache memory. ``make`` is
-    ``GraphedDecoder`` except in tests.
+    ``GraphedDecoder`` except in tests. A contrastive request keys on its k
+    (``penalty_alpha`` is a device buffer and no key).
 
     ``p.data_ptr()`` pins a cached graph to the current parameter storage:
     ``model.to(device/dtype)`` reallocates it, and a graph replaying against the
     old pointers would silently use stale weights (an in-place
     ``load_state_dict`` is fine, the graph holds parameter pointers)."""
     p = next(model.parameters())
-    key = (route.batch, route.bucket, p.device, p.dtype, p.data_ptr(), num_beams, route.ragged)
+    key = (route.batch, route.bucket, p.device, p.dtype, p.data_ptr(), num_beams, route.ragged,
+           contrastive_k)
     if route.baked:
         key += (do_sample, float(temperature), top_k)
     cache = getattr(owner, "_graph_decoders", None)
@@ -676,7 +839,7 @@ def decoder_for(owner, model, route: GraphRoute, num_beams: int = 1, do_sample=F
             model, allocate_kv_cache(model, route.batch, device=p.device, dtype=p.dtype,
                                      ca_capacity=route.bucket),
             do_sample=do_sample, temperature=temperature, top_k=top_k, num_beams=num_beams,
-            ragged=route.ragged)
+            ragged=route.ragged, **({"contrastive_k": contrastive_k} if contrastive_k else {}))
     return gd
 
 
@@ -686,11 +849,12 @@ def replay(gd: GraphedDecoder, n: int, eos_token_id: Optional[int] = None,
     ``decode(n)`` with no host synchronisation. With EOS the replays run in
     chunks of 16 with one look at ``finished`` between them (one sync per 16
     tokens) and stop once every row is done; the caller cuts the result where
-    the host loop would have stopped. Returns (batch, <= n) tokens, or None
-    with ``tokens=False``."""
+    the host loop would have stopped. Returns (rows, <= n) tokens, one row per
+    entry of ``finished`` (the batch, or the prompts of a contrastive decoder),
+    or None with ``tokens=False``."""
     if eos_token_id is None:
         return gd.decode(n, tokens=tokens)
-    chunks = [gd.tok[:, :0]]
+    chunks = [gd.tok.new_empty((gd.finished.shape[0], 0))]
     while n > 0 and not bool(gd.finished.all()):
         c = min(16, n)
         chunks.append(gd.decode(c, tokens=tokens))

@@ -284,6 +284,12 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
                                      length_penalty, use_cache, static_cache)
         if penalty_alpha is not None and penalty_alpha > 0 and top_k and top_k > 1 \
                 and not do_sample:
+            if use_cache and static_cache:
+                out = self._contrastive_search_graphed(input_ids, attention_mask, prefix_len,
+                                                       top_k, penalty_alpha, max_new_tokens,
+                                                       eos_token_id, pad_token_id)
+                if out is not None:
+                    return out
             return self._contrastive_search(input_ids, attention_mask, prefix_len,
                                             top_k, penalty_alpha, max_new_tokens,
                                             eos_token_id, pad_token_id, use_cache,
@@ -438,6 +444,34 @@ class PerceiverCausalSequenceModel(PreTrainedModel):
         best = (beam_scores / norm).argmax(dim=-1)
         idx = best + torch.arange(bsz, device=device) * num_beams
         return input_ids.index_select(0, idx)
+
+    @torch.no_grad()
+    def _contrastive_search_graphed(self, input_ids, attention_mask, prefix_len, top_k,
+                                    penalty_alpha, max_new_tokens, eos_token_id, pad_token_id):
+        """Contrastive search on the captured decode graph. Returns None when
+        ``graph_decode.graph_route`` refuses the request: the host loop
+        ``_contrastive_search`` runs then.
+
+        One decoder (captured graph + caches of ``bsz * top_k`` rows) is kept per
+        (bsz, top_k, bucket); ``penalty_alpha``, EOS and fill ids live in device
+        memory, so requests that differ in them or in prompt length replay the
+        same graph."""
+        bsz, seq_len = input_ids.shape
+        route = _graph.graph_route(
+            self.backend_model, bsz, seq_len, prefix_len, max_new_tokens,
+            attention_mask=attention_mask, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+            contrastive_k=top_k)
+        if route is None:
+            return None
+        gd = _graph.decoder_for(self, self.backend_model, route, contrastive_k=top_k)
+        # the host loop's fill: the pad id, else EOS, else 0
+        gd.set_sampling(penalty_alpha=penalty_alpha, eos_token_id=eos_token_id,
+                        pad_token_id=pad_token_id)
+        gd.prefill(input_ids, prefix_len=prefix_len)
+        new = _graph.replay(gd, max_new_tokens, eos_token_id)
+        if eos_token_id is not None:  # cut where the host loop would have stopped
+            new = self._cut_at_all_done(new, eos_token_id)
+        return torch.cat([input_ids, new], dim=1)
 
     @torch.no_grad()
     def _contrastive_search(self, input_ids, attention_mask, prefix_len, top_k,

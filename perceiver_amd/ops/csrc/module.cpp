@@ -61,6 +61,20 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 bool decode_attn_applicable(long D, long Dv);
 std::tuple<int64_t, int64_t> decode_attn_plan(int64_t B, int64_t H, int64_t cap, int64_t D);
 
+bool contrastive_applicable(long V, long k, long C);
+std::tuple<int64_t, int64_t> contrastive_plan(int64_t G, int64_t cap, int64_t C);
+torch::Tensor contrastive_sim(torch::Tensor h, torch::Tensor hist, torch::Tensor rnorm,
+                              torch::Tensor hist_len, int64_t k);
+void contrastive_commit(torch::Tensor logits, torch::Tensor tok, torch::Tensor prob, int64_t k,
+                        c10::optional<torch::Tensor> h, c10::optional<torch::Tensor> part,
+                        c10::optional<torch::Tensor> hist, c10::optional<torch::Tensor> rnorm,
+                        c10::optional<torch::Tensor> hist_len, c10::optional<torch::Tensor> done,
+                        c10::optional<torch::Tensor> src, c10::optional<torch::Tensor> alpha,
+                        c10::optional<torch::Tensor> eos_fill, c10::optional<torch::Tensor> step,
+                        c10::optional<torch::Tensor> rec, c10::optional<torch::Tensor> sim_out,
+                        c10::optional<torch::Tensor> score_out);
+void contrastive_copy(torch::Tensor table, torch::Tensor counters, torch::Tensor src, int64_t k);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gelu_bias_fwd", &gelu_bias_fwd, "fused bias+GELU forward (bf16)");
     m.def("gelu_bias_bwd", &gelu_bias_bwd, "fused bias+GELU backward (bf16)");
@@ -150,4 +164,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "per-group source beams",
           pybind11::arg("table"), pybind11::arg("counters"), pybind11::arg("src"),
           pybind11::arg("num_beams"));
+    m.def("contrastive_applicable",
+          [](int64_t V, int64_t k, int64_t C) { return contrastive_applicable(V, k, C); },
+          "host-only: whether the contrastive kernels take a vocabulary of V, k candidates and "
+          "hidden states of C channels");
+    m.def("contrastive_plan", &contrastive_plan,
+          "host-only: (nsplit, row granule) of contrastive_sim's static grid (nsplit, G)");
+    m.def("contrastive_sim", &contrastive_sim,
+          "per slice of the history the k maxima of dot(hist_t, h_j) * rnorm_t: (nsplit, G, 8) fp32",
+          pybind11::arg("h"), pybind11::arg("hist"), pybind11::arg("rnorm"),
+          pybind11::arg("hist_len"), pybind11::arg("k"));
+    m.def("contrastive_commit", &contrastive_commit,
+          "one contrastive-search step per group of k rows: score, select, record, append to the "
+          "history and propose the next k candidates; without h the proposal alone",
+          pybind11::arg("logits"), pybind11::arg("tok"), pybind11::arg("prob"), pybind11::arg("k"),
+          pybind11::arg("h") = pybind11::none(), pybind11::arg("part") = pybind11::none(),
+          pybind11::arg("hist") = pybind11::none(), pybind11::arg("rnorm") = pybind11::none(),
+          pybind11::arg("hist_len") = pybind11::none(), pybind11::arg("done") = pybind11::none(),
+          pybind11::arg("src") = pybind11::none(), pybind11::arg("alpha") = pybind11::none(),
+          pybind11::arg("eos_fill") = pybind11::none(), pybind11::arg("step") = pybind11::none(),
+          pybind11::arg("rec") = pybind11::none(), pybind11::arg("sim_out") = pybind11::none(),
+          pybind11::arg("score_out") = pybind11::none());
+    m.def("contrastive_copy", &contrastive_copy,
+          "copy the row at each described cache buffer's length counter from the selected row of "
+          "every group to the group's other rows",
+          pybind11::arg("table"), pybind11::arg("counters"), pybind11::arg("src"),
+          pybind11::arg("k"));
 }
