@@ -35,7 +35,7 @@ __global__ void ln_fwd_kernel(const unsigned short* __restrict__ x,
     unsigned short* yrow = y + row * C;
 
     float vals[CHUNKS][8];
-    float sum = 0.f, sumsq = 0.f;
+    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < CHUNKS; ++i) {
         if constexpr (ADD) {
@@ -44,22 +44,41 @@ __global__ void ln_fwd_kernel(const unsigned short* __restrict__ x,
                 float sv = bf2f(f2bf(v[0] + v[1]));
                 vals[i][e] = sv;
                 sum += sv;
-                sumsq += sv * sv;
             });
             store_granule_bf16(s + row * C, c0, C, [&](int e) { return vals[i][e]; });
         } else {
             visit_granule({xrow}, granule_col(lane, i), C, [&](int e, float (&v)[1]) {
                 vals[i][e] = v[0];
                 sum += v[0];
-                sumsq += v[0] * v[0];
             });
         }
     }
     sum = wave_sum(sum);
-    sumsq = wave_sum(sumsq);
     float mean = sum / C;
-    float var = sumsq / C - mean * mean;
-    float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+    // Variance from a centred second pass over the cached row, in range only.
+    // sumsq / C - mean * mean cancels mean^2 / var of the fp32 precision, up to
+    // 2^16 for bf16 rows that sit on two neighbouring values (docs/kernels.md).
+    float ssq = 0.f;
+#pragma unroll
+    for (int i = 0; i < CHUNKS; ++i) {
+        int c0 = granule_col(lane, i);
+        if (c0 + 8 <= C) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float d = vals[i][e] - mean;
+                ssq += d * d;
+            }
+        } else if (c0 < C) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (c0 + e < C) {
+                    float d = vals[i][e] - mean;
+                    ssq += d * d;
+                }
+        }
+    }
+    float var = wave_sum(ssq) / C;
+    float rstd = rsqrtf(var + eps);
     if (lane == 0) {
         mean_out[row] = mean;
         rstd_out[row] = rstd;
@@ -405,14 +424,26 @@ std::vector<torch::Tensor> add_ln_fwd(torch::Tensor h, torch::Tensor x, torch::T
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w,
                                   torch::Tensor mean, torch::Tensor rstd, bool needs_dwdb,
                                   c10::optional<torch::Tensor> ds) {
+    TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16,
+                "ln_bwd: dy must be cuda bf16");
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16, "ln_bwd: x must be cuda bf16");
+    TORCH_CHECK(dy.sizes() == x.sizes(), "ln_bwd: dy and x must have one shape");
+    TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16, "ln_bwd: w must be cuda bf16");
     dy = dy.contiguous(); x = x.contiguous();
     auto wc = w.contiguous();
     int C = x.size(-1);
+    TORCH_CHECK(C <= ROW_MAXC, "ln_bwd: C must be <= 2048");
+    TORCH_CHECK(wc.numel() == C, "ln_bwd: w must hold C elements");
     long rows = x.numel() / C;
+    TORCH_CHECK(mean.is_cuda() && mean.scalar_type() == torch::kFloat32 && mean.numel() == rows &&
+                rstd.is_cuda() && rstd.scalar_type() == torch::kFloat32 && rstd.numel() == rows,
+                "ln_bwd: mean and rstd must be cuda fp32 of one element per row");
+    mean = mean.contiguous(); rstd = rstd.contiguous();
     const bool has_ds = has_tensor(ds);
     if (has_ds) {
-        TORCH_CHECK(ds->scalar_type() == torch::kBFloat16 && ds->sizes() == x.sizes(),
-                    "ln_bwd: ds must be bf16 and shaped like x");
+        TORCH_CHECK(ds->is_cuda() && ds->scalar_type() == torch::kBFloat16 &&
+                        ds->sizes() == x.sizes(),
+                    "ln_bwd: ds must be cuda bf16 and shaped like x");
         ds = ds->contiguous();
     }
     auto dx = torch::empty_like(x);

@@ -287,6 +287,11 @@ def colsum_random_case(rows, C, seed=0):
     return (torch.randn(rows, C, generator=g) * 0.5).bfloat16()
 
 
+def colsum_depth(rows, nparts):
+    """Length of one column's fp32 summation chain, see colsum_bound."""
+    return -(-rows // nparts) + -(-nparts // 16) + 16
+
+
 def colsum_bound(x, nparts=None):
     """|got - ref| <= U*|ref| + depth * 2^-24 * sum_r |x[r, c]|, ref the fp64
     column sum of the bf16 input.
@@ -297,7 +302,7 @@ def colsum_bound(x, nparts=None):
     partial sum of magnitude <= sum|x| by 2^-24."""
     rows = x.shape[0]
     nparts = colsum_nparts(rows) if nparts is None else nparts
-    depth = -(-rows // nparts) + -(-nparts // 16) + 16
+    depth = colsum_depth(rows, nparts)
     xd = x.double()
     return U * xd.sum(0).abs() + depth * F32 * xd.abs().sum(0)
 

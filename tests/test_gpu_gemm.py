@@ -8,6 +8,8 @@ bf16-rounded outputs must match the fp32 reference to bf16 resolution).
 import pytest
 import torch
 
+import _norm_gemm_ref as NG
+
 pytestmark = pytest.mark.gpu
 
 
@@ -49,6 +51,10 @@ def test_gemm_bt_parity(M, N, K, bias):
     # exact-match rate against the fp32-then-round reference should be high
     match = (y == ref).float().mean().item()
     assert match > 0.98, match
+    # the derived bound of tests/_norm_gemm_ref.py against fp64
+    xc, wc, bc = x.cpu(), w.cpu(), None if b is None else b.cpu()
+    ratio = NG.worst_ratio(y.cpu(), NG.gemm_ref(xc, wc, bc), NG.gemm_bound(xc, wc, bc))
+    assert ratio <= 1.0, ratio
 
 
 def test_perceiver_linear_dgrad_routes_custom():
@@ -131,6 +137,12 @@ def test_gemm_bt_bn160_path():
         ref = _ref(x, w, b)
         match = (y == ref).float().mean().item()
         assert match > 0.98, (M, N, K, match)
+        # 20 workgroups of 256x128 waste fewer slots of a round than 16 of 256x160,
+        # so (512, 1280) takes the 128 tile; the other two can only take 160
+        assert NG.gemm_tile_width(M, N) == (128 if N == 1280 else 160)
+        ratio = NG.worst_ratio(y.cpu(), NG.gemm_ref(x.cpu(), w.cpu(), b.cpu()),
+                               NG.gemm_bound(x.cpu(), w.cpu(), b.cpu()))
+        assert ratio <= 1.0, (M, N, K, ratio)
 
 
 def test_transpose_bf16():

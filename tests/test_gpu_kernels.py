@@ -6,6 +6,8 @@ import math
 import pytest
 import torch
 
+import _norm_gemm_ref as NG
+
 pytestmark = pytest.mark.gpu
 
 
@@ -173,6 +175,10 @@ def test_fused_layer_norm_matches_torch():
         # C = 322 ends in a ragged granule: the kernel walks it element-wise
         y, mean, rstd = _ext().ln_fwd(x.bfloat16(), w.bfloat16(), b.bfloat16(), 1e-5)
         assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2), C
+        # the derived bounds of tests/_norm_gemm_ref.py, from the bf16 inputs
+        xb, wb, bb = x.bfloat16().cpu(), w.bfloat16().cpu(), b.bfloat16().cpu()
+        ratios = NG.ln_fwd_ratios(xb, wb, bb, y.cpu(), mean.cpu(), rstd.cpu())
+        assert max(ratios) <= 1.0, (C, ratios)
 
         xf = x.clone().requires_grad_()
         wf = w.clone().requires_grad_()
@@ -182,6 +188,9 @@ def test_fused_layer_norm_matches_torch():
         out.backward(dy)
         dx, dw, db = _ext().ln_bwd(dy.bfloat16(), x.bfloat16(), w.bfloat16(), mean, rstd, True)
         assert torch.allclose(dx.float(), xf.grad, atol=5e-2, rtol=5e-2), C
+        ratios = NG.ln_bwd_ratios(dy.bfloat16().cpu(), xb, wb, mean.cpu(), rstd.cpu(),
+                                  dx.cpu(), dw.cpu(), db.cpu())
+        assert max(ratios) <= 1.0, (C, ratios)
         # dw/db are 400-term reductions of bf16 products: scale the absolute
         # budget by the reduction magnitude instead of a flat atol=0.5 that
         # could hide a real bug at small magnitudes
@@ -214,8 +223,14 @@ def test_layer_norm_ragged_and_multichunk_rows(rows, C):
 
     y, mean, rstd = _ext().ln_fwd(x, w, b, 1e-5)
     assert torch.allclose(y.float(), ref.detach(), atol=3e-2, rtol=3e-2)
+    cpu = [t.cpu() for t in (dy, x, w, mean, rstd)]
+    ratios = NG.ln_fwd_ratios(x.cpu(), w.cpu(), b.cpu(), y.cpu(), mean.cpu(), rstd.cpu())
+    assert max(ratios) <= 1.0, ratios  # the derived bounds of tests/_norm_gemm_ref.py
     dx, dw, db = _ext().ln_bwd(dy, x, w, mean, rstd, True)
     dx_only = _ext().ln_bwd(dy, x, w, mean, rstd, False)[0]
+    ratios = NG.ln_bwd_ratios(*cpu, dx.cpu(), dw.cpu(), db.cpu()) \
+        + NG.ln_bwd_ratios(*cpu, dx_only.cpu())
+    assert max(ratios) <= 1.0, ratios
     for got in (dx, dx_only):
         assert got.shape == x.shape
         assert torch.allclose(got.float(), xf.grad, atol=5e-2, rtol=5e-2)
@@ -236,6 +251,9 @@ def test_layer_norm_module_dispatch():
     ref = torch.nn.functional.layer_norm(x.float().detach(), (768,),
                                          ln.weight.float(), ln.bias.float(), ln.eps)
     assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2)
+    y_ref, _ = NG.ln_y_ref(x.detach().cpu(), ln.weight.detach().cpu(), ln.bias.detach().cpu(), ln.eps)
+    bound = NG.ln_y_bound(x.detach().cpu(), ln.weight.detach().cpu(), ln.bias.detach().cpu(), ln.eps)
+    assert NG.worst_ratio(y.detach().cpu(), y_ref, bound) <= 1.0
     assert x.grad is not None and ln.weight.grad is not None
 
 

@@ -11,6 +11,8 @@ output tiles (256x128 and 256x256).
 import pytest
 import torch
 
+import _norm_gemm_ref as NG
+
 pytestmark = pytest.mark.gpu
 
 K_STEP = 64
@@ -31,13 +33,24 @@ def _check_dw(dw, dy, x):
     assert (err / scale).max().item() < 2e-2, (err.max().item(), (err / scale).max().item())
     match = (dw == ref).float().mean().item()
     assert match > 0.98, match
+    # the derived bound of tests/_norm_gemm_ref.py against fp64
+    nsplit = _ext().wgrad_plan(dy.shape[0], dy.shape[1], x.shape[1])[2]
+    ratio = NG.worst_ratio(dw.cpu(), NG.wgrad_ref(dy.cpu(), x.cpu())[0],
+                           NG.wgrad_bound(dy.cpu(), x.cpu(), nsplit))
+    assert ratio <= 1.0, ratio
 
 
-def _check_db(db, dy):
+def _check_db(db, dy, x):
     # bounds of tests/test_gpu_kernels.py::test_colsum_matches_torch_sum
     want = dy.float().sum(0).bfloat16().float()
     assert db.dtype == torch.bfloat16 and db.shape == want.shape
     torch.testing.assert_close(db.float(), want, atol=4.0, rtol=1e-2)
+    # colsum_bound with the chain of the fused sum (tests/_norm_gemm_ref.py);
+    # x only says which plan the launch used
+    _, _, nsplit, rows = _ext().wgrad_plan(dy.shape[0], dy.shape[1], x.shape[1])
+    ratio = NG.worst_ratio(db.cpu(), dy.cpu().double().sum(0),
+                           NG.wgrad_db_bound(dy.cpu(), nsplit, rows))
+    assert ratio <= 1.0, ratio
 
 
 # (M, N, K, tile_k, nsplit, rows_per_split) — the plan is pinned so a planner
@@ -65,7 +78,7 @@ def test_gemm_wgrad_parity(M, N, K, tile_k, nsplit, rows, want_db):
     assert len(out) == (2 if want_db else 1)
     _check_dw(out[0], dy, x)
     if want_db:
-        _check_db(out[1], dy)
+        _check_db(out[1], dy, x)
 
 
 def test_gemm_wgrad_is_deterministic():
@@ -103,7 +116,7 @@ def test_wrapper_takes_non_contiguous_dy():
     y = _ColsumLinearFn.apply(x, w, b)
     y.backward(dy)
     _check_dw(w.grad, dy.contiguous(), x)
-    _check_db(b.grad, dy.contiguous())
+    _check_db(b.grad, dy.contiguous(), x)
 
 
 def _grads(make_out, params, dy):
@@ -139,7 +152,7 @@ def test_perceiver_linear_wgrad_matches_lever_off(monkeypatch):
     for got, ref, tol in zip(new, old, (1e-2, 2e-2, 2e-2)):
         _assert_close_bf16_paths(got, ref, tol)
     _check_dw(new[1], dy, x.detach())
-    _check_db(new[2], dy)
+    _check_db(new[2], dy, x.detach())
 
 
 def test_linear_gelu_bias_wgrad_matches_lever_off(monkeypatch):
